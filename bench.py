@@ -6,7 +6,13 @@ including the end-of-cycle residual norm (MLAMG.py:194). Setup (aggregation, lam
 prolongators, Galerkin, dense coarse inverse) runs on the GPU before timing and is reported
 separately.
 
-  python bench.py [--gpus N --steps K --warmup W] [--n 216] [--no-cpu-baseline]
+  python bench.py [--gpus N --steps K --warmup W] [--n 216] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR
+then writes what the last timed step left in the caller's hands (the iterate x) as DIR/x.npy.
+--full adds every other measurement to the line: the convergence sample, the general-b and
+factored-P0 cycles, the fine-SpMV roofline and format A/B, the PCIe-inclusive solve, the
+unstructured (C3) and variable-coefficient lines and the CPU baselines.
 
 N > 1: one process per GPU — launched by torch.distributed.run (RANK/WORLD_SIZE/... in the
 environment), or, when started as plain `python bench.py --gpus N`, by bench.py itself: it
@@ -35,6 +41,31 @@ import torch  # noqa: E402
 
 METRIC = "V-cycles/sec + fine-level SpMV GB/s (%HBM peak), 3D Laplace 10M DoF"
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+
+
+DUMP_MAX_BYTES = 32 << 20  # per dumped array; larger outputs are sampled
+DUMP_SEED = 20240607
+
+
+def dump_array(a):
+    """The array --dump-outputs stores for output `a` (flattened, float32 kept, everything else
+    float64): `a` itself up to DUMP_MAX_BYTES, otherwise its entries at DUMP_MAX_BYTES / itemsize
+    positions drawn once from RandomState(DUMP_SEED) without replacement, in ascending order —
+    the same positions for the same length, so two builds are compared entry for entry."""
+    a = np.asarray(a)
+    a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64).ravel()
+    keep = DUMP_MAX_BYTES // a.itemsize
+    if a.size <= keep:
+        return a
+    idx = np.sort(np.random.RandomState(DUMP_SEED).choice(a.size, size=keep, replace=False))
+    return a[idx]
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output of the timed path."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), dump_array(a))
 
 
 def log(*a):
@@ -198,7 +229,7 @@ def cpu_baseline_parallel(H, b_host, x_host, cycles, threads):
     return cycles / dt, dt, hist
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -214,6 +245,16 @@ def main():
     ap.add_argument("--coarse-order", choices=("sorted", "seed"), default="sorted",
                     help="aggregation='reference': level-0 coarse unknowns in ascending seed "
                          "order (same aggregates, relabelled) or nearest_center_to_agg's order")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run every other measurement and check of the "
+                         "benchmark (convergence sample, general-b and factored-P0 cycles, "
+                         "fine-SpMV roofline and format A/B, PCIe-inclusive solve, C3 and "
+                         "variable-coefficient lines, CPU baselines); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (the "
+                         "iterate x the caller's buffer holds) as DIR/x.npy (float64; a fixed "
+                         "seeded sample of its entries when x is larger than "
+                         f"{DUMP_MAX_BYTES >> 20} MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-cycles", type=int, default=20)
     ap.add_argument("--cpu-par-cycles", type=int, default=10)
@@ -243,11 +284,15 @@ def main():
     ap.add_argument("--verify-selftest", action="store_true",
                     help="run the distributed verification chain over gloo (mismatch injected "
                          "by MLAMG_INJECT_MISMATCH_RANK); no GPU work")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.dist):
+        ap.error("--dump-outputs is for the single-GPU run (no --dist, --gpus 1)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher (nothing has touched the GPU)
-        sys.exit(self_launch(args.gpus, sys.argv[1:]))
+        sys.exit(self_launch(args.gpus, sys.argv[1:] if argv is None else list(argv)))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -285,10 +330,16 @@ def main():
     b = torch.zeros(n, dtype=torch.float64, device="cuda")
     x = torch.as_tensor(x0).cuda()
     use_graph = not args.no_graph
-    # convergence sample (also warms the graph)
-    hist = H.cycle(b, x, 10, use_graph=use_graph)
-    conv = float((hist[-1] / hist[-4]) ** (1.0 / 3.0)) if len(hist) >= 4 else float("nan")
-    log(f"residual history (10 cycles): {hist[0]:.3e} -> {hist[-1]:.3e}, conv factor {conv:.4f}")
+    hist = conv = None
+    if args.full:
+        # convergence sample (also warms the graph)
+        hist = H.cycle(b, x, 10, use_graph=use_graph)
+        conv = float((hist[-1] / hist[-4]) ** (1.0 / 3.0)) if len(hist) >= 4 else float("nan")
+        log(f"residual history (10 cycles): {hist[0]:.3e} -> {hist[-1]:.3e}, "
+            f"conv factor {conv:.4f}")
+    else:
+        # one untimed cycle: the graph capture and first launches happen here, not in a step
+        H.cycle_async(b, x, 1, use_graph=use_graph)
     x.copy_(torch.as_tensor(x0))
     H.cycle_async(b, x, args.warmup, use_graph=use_graph)
     torch.cuda.synchronize()
@@ -298,7 +349,63 @@ def main():
     dt = time.perf_counter() - t0
     cycles_per_s = args.steps / dt
     ms_per_step = dt / args.steps * 1e3
-    cyc_fmt_bytes_timed, cyc_bytes_timed = H.cycle_bytes(stored=True), H.cycle_bytes()
+    if args.dump_outputs:
+        # the timed call's only output: the iterate it left in the caller's x
+        dump_outputs(args.dump_outputs, {"x": x.cpu().numpy()})
+    A0 = H.levels[0].A
+    cyc_bytes = H.cycle_bytes()                # operators priced as CSR (§8(d)), the timed b
+    cyc_fmt_bytes = H.cycle_bytes(stored=True)  # operators priced as stored: HBM bytes
+    t_cycle = dt / args.steps
+    out = {
+        "metric": METRIC,
+        "value": round(cycles_per_s, 3),
+        "unit": "V-cycles/s",
+        "n_gpus": 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"C4: 3D 7-point Laplace {n1}^3 ({n} DoF, nnz {A0.nnz}), SA-AMG "
+                        f"V(1,1) weighted Jacobi w=2/3, seeded Bellman-Ford aggregates "
+                        f"alpha={args.alpha} ({aggregation_rule(args)}), {H.n_levels} levels, "
+                        f"dense coarse n={H.Ac.shape[0]}",
+                "aggregation": args.aggregation, "coarse_order": args.coarse_order,
+            "n": n, "nnz": A0.nnz, "levels": H.n_levels,
+            "operator_complexity": round(H.operator_complexity(), 4),
+            "parallelism": "single GPU",
+        },
+        # whole cycle: the bytes its launches must move as stored (every operator's format
+        # bytes + the epilogue vectors) over the cycle time = the cycle's HBM fraction; the
+        # CSR-priced figure is a CSR-EQUIVALENT rate (re-encoded operators move fewer bytes,
+        # so it can exceed the peak) and is labelled as such
+        "cycle_format_bytes": cyc_fmt_bytes,
+        "cycle_hbm_GBps": round(cyc_fmt_bytes / t_cycle / 1e9, 1),
+        "cycle_hbm_frac": round(cyc_fmt_bytes / t_cycle / 1e9 / HBM_PEAK_GBPS, 4),
+        "cycle_csr_bytes": cyc_bytes,
+        "cycle_csr_equivalent_GBps": round(cyc_bytes / t_cycle / 1e9, 1),
+        "operator_formats": [{k: v[0] + (f"/{v[1]}" if v[1] else "") for k, v in f.items()}
+                             for f in H.formats()],
+        "format_autotune_us": H.tuning,
+        "setup_s": {k: round(v, 3) for k, v in H.timings.items()},
+        "setup_galerkin_s_per_level": H.galerkin_s,
+        "setup_spgemm_phases_ms": H.spgemm_phases_ms,
+        "rhs": "b = 0 (x0 = RandomState(0).randn normalised): passed to the cycle as NULL, the "
+               "fine-level kernels read no b vector (same bits as streaming zeros)",
+    }
+    if args.full:
+        full_lines(out, args, H, A, b, x, x0, hist, conv, use_graph)
+    print(json.dumps(out), flush=True)
+
+
+def full_lines(out, args, H, A, b, x, x0, hist, conv, use_graph):
+    """--full: every measurement and check beside the headline, each a run of its own after the
+    timed steps, added to the result line `out`."""
+    n = A.shape[0]
     # the same cycles with b streamed as a vector (the general right-hand-side kernels): the
     # headline's b is zero (SURVEY.md §8(d): b = 0, utils/common.py:74), which the cycle takes
     # as NULL (hierarchy.rhs_arg) and never reads — identical bits (tests/test_gpu_hierarchy.py
@@ -344,32 +451,7 @@ def main():
     # only a PMC measurement of this very kernel (same format, same operator size) applies
     traffic = (pmc.get("hbm_bytes_per_launch")
                if pmc and pmc.get("algorithmic_bytes_per_launch") == B_fmt else None)
-    cyc_bytes = cyc_bytes_timed          # operators priced as CSR (§8(d)), the timed call's b
-    cyc_fmt_bytes = cyc_fmt_bytes_timed  # operators priced as stored: HBM bytes
-    t_cycle = dt / args.steps
-    out = {
-        "metric": METRIC,
-        "value": round(cycles_per_s, 3),
-        "unit": "V-cycles/s",
-        "n_gpus": 1,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"C4: 3D 7-point Laplace {n1}^3 ({n} DoF, nnz {A0.nnz}), SA-AMG "
-                        f"V(1,1) weighted Jacobi w=2/3, seeded Bellman-Ford aggregates "
-                        f"alpha={args.alpha} ({aggregation_rule(args)}), {H.n_levels} levels, "
-                        f"dense coarse n={H.Ac.shape[0]}",
-                "aggregation": args.aggregation, "coarse_order": args.coarse_order,
-            "n": n, "nnz": A0.nnz, "levels": H.n_levels,
-            "operator_complexity": round(H.operator_complexity(), 4),
-            "parallelism": "single GPU",
-        },
+    out.update({
         "roofline": {
             "bound": "hbm",
             "kernel": f"fine-level SpMV, y = A x ({fmt0} kernel, scipy summation order)",
@@ -389,15 +471,6 @@ def main():
             "warm_avg_launch_us": round(t_warm * 1e6, 2),
             "warm_frac": round(B_fmt / t_warm / 1e9 / HBM_PEAK_GBPS, 4),
         },
-        # whole cycle: the bytes its launches must move as stored (every operator's format
-        # bytes + the epilogue vectors) over the cycle time = the cycle's HBM fraction; the
-        # CSR-priced figure is a CSR-EQUIVALENT rate (re-encoded operators move fewer bytes,
-        # so it can exceed the peak) and is labelled as such
-        "cycle_format_bytes": cyc_fmt_bytes,
-        "cycle_hbm_GBps": round(cyc_fmt_bytes / t_cycle / 1e9, 1),
-        "cycle_hbm_frac": round(cyc_fmt_bytes / t_cycle / 1e9 / HBM_PEAK_GBPS, 4),
-        "cycle_csr_bytes": cyc_bytes,
-        "cycle_csr_equivalent_GBps": round(cyc_bytes / t_cycle / 1e9, 1),
         # the same fine SpMV in the generic CSR-stream kernel (no stencil re-encoding: what an
         # arbitrary CSR operator gets)
         "roofline_generic_csr": {
@@ -407,18 +480,10 @@ def main():
             "algorithmic_bytes_per_launch": ab["csr_stream"]["format_bytes"],
             "avg_launch_us": ab["csr_stream"]["us"]},
         "fine_spmv_formats": ab,
-        "operator_formats": [{k: v[0] + (f"/{v[1]}" if v[1] else "") for k, v in f.items()}
-                             for f in H.formats()],
-        "format_autotune_us": H.tuning,
-        "setup_s": {k: round(v, 3) for k, v in H.timings.items()},
-        "setup_galerkin_s_per_level": H.galerkin_s,
-        "setup_spgemm_phases_ms": H.spgemm_phases_ms,
         "conv_factor_10cycles": round(conv, 5),
-        "rhs": "b = 0 (x0 = RandomState(0).randn normalised): passed to the cycle as NULL, the "
-               "fine-level kernels read no b vector (same bits as streaming zeros)",
         "general_rhs": general_rhs,
         "factored_p0": factored,
-    }
+    })
     # host-buffer boundary: solve() on numpy b/x0 pays the PCIe copies of b
     # and x0 in and x out around its cycles; 10 cycles per call, the same hierarchy
     b_h0 = np.zeros(n)
@@ -460,7 +525,6 @@ def main():
                       f"this process may use ({cores_desc}), {dtp:.1f}s; "
                       f"residuals agree with GPU: {agree_p}",
         }
-    print(json.dumps(out), flush=True)
 
 
 def factored_p0_line(H, b, x, x0, hist, args, use_graph):
@@ -629,7 +693,7 @@ def run_distributed(args, world, rank, local_rank):
         out, H, x0, teardown = distributed.bench_main(args, world, rank, local_rank, METRIC,
                                                       HBM_PEAK_GBPS, phases=ph)
         if rank == 0:
-            if not args.no_cpu_baseline and H is not None:
+            if args.full and not args.no_cpu_baseline and H is not None:
                 # rank 0 only, on the same (replicated) hierarchy; the others wait in teardown
                 n = x0.shape[0]
                 v, dtc, hcpu = cpu_baseline(H, np.zeros(n), x0, args.cpu_cycles)

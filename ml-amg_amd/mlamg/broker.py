@@ -106,11 +106,36 @@ _client_sock = None
 _client_pid = None
 
 
+_SUN_PATH_MAX = 100  # sockaddr_un.sun_path holds 108 bytes on Linux, the final NUL included
+
+
+class _sock_addr:
+    """The address to bind or connect a Unix socket at `path`: the path itself, or, when it is
+    too long for sockaddr_un (a deep temp dir), the same file named through a descriptor of its
+    directory (/proc/self/fd/<fd>/<name>), open for the duration of the `with` block."""
+
+    def __init__(self, path):
+        self.path, self.fd = path, None
+
+    def __enter__(self):
+        if len(os.fsencode(self.path)) <= _SUN_PATH_MAX:
+            return self.path
+        d, name = os.path.split(self.path)
+        self.fd = os.open(d or ".", os.O_RDONLY | os.O_DIRECTORY)
+        return f"/proc/self/fd/{self.fd}/{name}"
+
+    def __exit__(self, *exc):
+        if self.fd is not None:
+            os.close(self.fd)
+        return False
+
+
 def _connect(path, timeout=None):
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     try:
         s.settimeout(timeout)
-        s.connect(path)
+        with _sock_addr(path) as addr:
+            s.connect(addr)
         s.settimeout(None)
         return s
     except OSError:
@@ -135,16 +160,18 @@ def _start_broker(path):
             env["PYTHONPATH"] = pkg_root + os.pathsep + env.get("PYTHONPATH", "")
             env.pop(ENV, None)  # the broker itself solves on the GPU
             log = open(path + ".log", "ab")
-            subprocess.Popen([sys.executable, "-m", "mlamg.broker", "--serve", path,
-                              "--device", str(device_index())],
-                             stdin=subprocess.DEVNULL, stdout=log, stderr=log, env=env,
-                             start_new_session=True, close_fds=True)
+            child = subprocess.Popen([sys.executable, "-m", "mlamg.broker", "--serve", path,
+                                      "--device", str(device_index())],
+                                     stdin=subprocess.DEVNULL, stdout=log, stderr=log, env=env,
+                                     start_new_session=True, close_fds=True)
             log.close()
             deadline = time.monotonic() + float(os.environ.get("MLAMG_BROKER_START_S", "300"))
             while time.monotonic() < deadline:  # the first torch import on a fresh box is slow
                 s = _connect(path)
                 if s is not None:
                     return s
+                if child.poll() is not None:  # it died before listening: do not wait it out
+                    break
                 time.sleep(0.05)
             raise BrokerError(f"the amg_2_v broker did not start (log: {path}.log)")
         finally:
@@ -296,7 +323,8 @@ class _Server:
         except FileNotFoundError:
             pass
         srv = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
-        srv.bind(self.path)
+        with _sock_addr(self.path) as addr:
+            srv.bind(addr)
         os.chmod(self.path, 0o600)  # this user's workers only
         srv.listen(256)
         with open(self.path + ".pid", "w") as fh:

@@ -109,6 +109,28 @@ def test_broker_death_raises(broker_env, monkeypatch):
     os.unlink(pid_file)
 
 
+def test_socket_dir_longer_than_sun_path(broker_env, tmp_path, monkeypatch):
+    """A socket directory whose path does not fit sockaddr_un (108 bytes; a deep temp dir): the
+    broker still starts, answers and shuts down."""
+    broker = broker_env
+    deep = tmp_path / ("d" * 60) / ("e" * 60)
+    deep.mkdir(parents=True)
+    monkeypatch.setenv("MLAMG_BROKER_DIR", str(deep))
+    monkeypatch.setenv("MLAMG_BROKER_BACKEND", "test-echo")
+    monkeypatch.setenv("MLAMG_BROKER_START_S", "60")
+    assert len(os.fsencode(broker.socket_path())) > 108
+    A, P, b, x = _problem()
+    xo, conv, err, it = broker.solve(A, P, b, x, {"res_tol": 1e-10})
+    assert np.array_equal(xo, x) and conv == 0.5 and it == 1
+    assert os.path.exists(broker.socket_path())
+    assert broker.shutdown()
+    for _ in range(100):
+        if not os.path.exists(broker.socket_path()):
+            break
+        time.sleep(0.05)
+    assert not os.path.exists(broker.socket_path())
+
+
 def test_amg_2_v_routes_to_broker(broker_env, monkeypatch):
     """mlamg.multigrid.amg_2_v with MLAMG_BROKER=1 hands the call over (the echo backend's
     answer comes back through the reference's return tuple)."""

@@ -130,9 +130,8 @@ def test_lloyd_aggregation_driver(golden, oracle):
 def test_gridio_matches_golden(golden):
     import os
     from mlamg import gridio
-    path = "/root/reference/demos/laplace_3d.grid"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
+    # the reference's demos/laplace_3d.grid, stored unchanged beside the golden vectors
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "laplace_3d.grid")
     A, x, extra = gridio.load_grid(path)
     assert np.array_equal(A.data, golden["lap3d_data"])
     assert np.array_equal(A.indices, golden["lap3d_indices"])

@@ -25,8 +25,8 @@ for step in "$@"; do
   case "$step" in
     suite) step="suite:900:$PYT tests" ;;
     smoke) step="smoke:300:python __graft_entry__.py smoke" ;;
-    bench) step="bench:600:python bench.py > $OUT/bench.json" ;;
-    prof) step="prof:600:rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o p -- python bench.py --steps 20 --no-cpu-baseline > $OUT/prof_bench.json" ;;
+    bench) step="bench:600:python bench.py --full > $OUT/bench.json" ;;
+    prof) step="prof:600:rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o p -- python bench.py --full --steps 20 --no-cpu-baseline > $OUT/prof_bench.json" ;;
     pytest=*) step="pytest_$(basename "${step#pytest=}" .py | tr -c 'A-Za-z0-9_\n' _):900:$PYT ${step#pytest=}" ;;
   esac
   name=${step%%:*}

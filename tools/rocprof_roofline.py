@@ -1,5 +1,5 @@
-"""The roofline kernel's launches in a rocprofv3 kernel trace of bench.py, against bench.py's own
-HIP-event figure (host-side analysis).
+"""The roofline kernel's launches in a rocprofv3 kernel trace of `bench.py --full` (the roofline
+measurement is part of --full only), against bench.py's own HIP-event figure (host-side analysis).
 
   python tools/rocprof_roofline.py <kernel_trace.csv> <bench.json line file> [out_stats.csv]
 
