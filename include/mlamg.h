@@ -559,6 +559,65 @@ int mlamg_hier_cycle_bytes(const mlamg_hier* H, double* bytes);
  * in (mlamg_csr_format_bytes per launch + the epilogues' vectors): the cycle's roofline bytes */
 int mlamg_hier_cycle_format_bytes(const mlamg_hier* H, double* bytes);
 
+/* ---------------------------------------------------------------- multi-vector (n x k) path
+ * A multivector is fp64, row-major n x k with a leading dimension ld >= k counted in doubles
+ * (a contiguous torch (n, k) tensor, or a column slice of a wider one; the layout of the
+ * reference's test-vector block, ns/model/loss.py:59). 1 <= k <= MLAMG_MV_MAX. Pointers need
+ * only be 8-byte aligned and ld may be odd (16-byte accesses are used where alignment allows).
+ * Every row is summed per column left to right in stored order with separate multiply and add,
+ * i.e. scipy's csr_matvecs: COLUMN j OF EVERY RESULT IS BITWISE THE SINGLE-VECTOR RESULT ON
+ * COLUMN j. The kernels read the CSR arrays and the row-block table, which every exact format
+ * keeps, so they do not depend on the format active on the handle; the matrix stream is read
+ * once for all k columns. All entries are async on `stream`; NULL arguments, k out of range and
+ * ld < k return MLAMG_EINVAL before any device call. */
+#define MLAMG_MV_MAX 64
+
+/* Y = alpha*A@X + beta*Y (X: n_cols x k, Y: n_rows x k). alpha==1 && beta==0 gives A@X bit for
+ * bit per column (ns/model/loss.py:70,78 `A @ x` on an N x k block). */
+int mlamg_spmm(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
+               double alpha, double beta, void* stream);
+
+/* R = B - A@X. B may be NULL: a zero right-hand side taken as +0.0 (the bits of the single path).
+ * norms (DEVICE, k doubles, nullable): ||R[:, j]||_2 in mlamg_norm2's order. */
+int mlamg_residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X,
+                      int64_t ldx, double* R, int64_t ldr, int k, double* norms, void* stream);
+
+/* nu weighted-Jacobi sweeps X += dinv_w .* (B - A@X) on every column (dinv_w: one vector of n,
+ * shared; the two roundings of mlamg_jacobi: r = b - s; x + d*r). X_tmp: scratch n x k with
+ * leading dimension ldt. Result lands in X. B may be NULL (zero right-hand side). */
+int mlamg_jacobi_mv(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb,
+                    double* X, int64_t ldx, double* X_tmp, int64_t ldt, int k, int nu,
+                    void* stream);
+
+/* Bc = R@Rf (mlamg_restrict per column) and X += P@E (mlamg_prolong_add per column). */
+int mlamg_restrict_mv(const mlamg_csr* R, const double* Rf, int64_t ldr, double* Bc, int64_t ldb,
+                      int k, void* stream);
+int mlamg_prolong_add_mv(const mlamg_csr* P, const double* E, int64_t lde, double* X, int64_t ldx,
+                         int k, void* stream);
+
+/* out[j] (DEVICE, k doubles) = ||X[:, j]||_2, bitwise mlamg_norm2 of that column. */
+int mlamg_norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, void* stream);
+
+/* X[:, j] -= mean(X[:, j]), bitwise mlamg_remove_mean of that column. */
+int mlamg_remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, void* stream);
+
+/* X = A_c^-1 B for the three mlamg_dense_info methods, per column bitwise mlamg_dense_solve; the
+ * dense operator is read once for all k columns. Not reentrant on one handle (method 2). */
+int mlamg_dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X,
+                         int64_t ldx, int k, void* stream);
+
+/* n_cycles V(nu1,nu2) cycles of a finalised hierarchy on the block (B, X), X updated in place:
+ * the step sequence of mlamg_hier_vcycle on every column, hence its bits. B may be NULL (zero
+ * right-hand side). remove_mean != 0 subtracts each column's mean after the post-smoothing of
+ * every cycle (ns/model/loss.py:89; ns/lib/multigrid.py:186-187). hist (DEVICE, n_cycles x k
+ * row-major, nullable) receives after each cycle, per column, ||b - A x||_2 (norm_mode 0) or
+ * ||x||_2 (norm_mode 1), taken after the mean removal. A fixed cycle count (no tolerance stop),
+ * run eagerly. MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother, a PCG or GMRES coarse
+ * solve, a factored prolongation, or any operator in the VECTOR format. */
+int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
+                         int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
+                         void* stream);
+
 /* ---------------------------------------------------------------- multi-GPU (RCCL over xGMI)
  * New relative to the reference, whose only parallelism is a process task farm over independent
  * grids (ns/parallel/pool.py:139-186, pickled objects over pipes / mpi4py, no collectives).

@@ -370,6 +370,24 @@ int norm_hist_impl(const double* x, int64_t n, double* partial, double* hist, in
                    int32_t* done, double tol, hipStream_t s);
 int count_out_of_range(const int32_t* a, int64_t n, int64_t lo, int64_t hi, hipStream_t s,
                        int64_t* bad_out);
+// multi-vector (row-major n x k, leading dimension ld) building blocks of the block V-cycle
+// (spmm.hip); per column the bits of the single-vector functions above
+int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
+                double alpha, double beta, hipStream_t s);
+int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
+                hipStream_t s);
+int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                double* R, int64_t ldr, int k, hipStream_t s);
+int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
+                    const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
+                    hipStream_t s);
+// mode 0: X += d .* R (jacobi_from_residual), mode 1: X = d .* R (jacobi_from_zero)
+int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ldr, int64_t n,
+            int k, int mode, hipStream_t s);
+int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStream_t s);
+int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s);
+int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X, int64_t ldx,
+                   int k, double* ytmp, hipStream_t s);
 // Cycles are launched in batches; with a tolerance, the device-side stop flag is read back
 // after each batch so the cycles after convergence are not launched at all (each would only
 // check the flag and return, ~10 launches apiece). Batches grow 4, 4, 8, 16, 32, 32, ...: at

@@ -92,6 +92,9 @@ struct mlamg_hier {
   // zero right-hand side for the paths that read b as a vector (Gauss-Seidel, coarse-only)
   double* zero_b = nullptr;
   bool zero_rhs = false;  // the last mlamg_hier_vcycle had b = NULL (cycle_bytes prices that)
+  // k-wide copies of the level vectors for mlamg_hier_vcycle_mv, grown on demand
+  void* mv_mem = nullptr;
+  size_t mv_bytes = 0;
 };
 
 
@@ -384,7 +387,205 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
 }
 }  // namespace mlamg
 
+// ---------------------------------------------------------------- block (n x k) cycle
+// The step sequence of cycle_top / cycle_coarse on a row-major block of k vectors, through the
+// multi-vector kernels of spmm.hip. The fusions of the single path (first sweep written by the
+// restriction or the end-of-cycle residual kernel) are left out: they are the same roundings, so
+// column j keeps the bits of the single-vector cycle on column j. Work buffers are k-wide copies
+// of the level vectors with leading dimension k.
+namespace {
+struct MvLevel {
+  double* x = nullptr;    // l > 0: iterate
+  double* b = nullptr;    // l > 0: right-hand side
+  double* r = nullptr;    // residual
+  double* tmp = nullptr;  // ping-pong partner of x
+};
+struct MvWork {
+  std::vector<MvLevel> lv;
+  double* xc = nullptr;
+  double* bc = nullptr;
+  double* yc = nullptr;  // dense method 2: the intermediate X b
+  double* r0 = nullptr;  // coarse-only hierarchy: residual of the history
+  int k = 0;
+};
+
+static int mv_unsupported(const char* why) {
+  set_error(std::string("mlamg_hier_vcycle_mv: ") + why);
+  return MLAMG_EUNSUPPORTED;
+}
+
+static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
+  const size_t nl = H->lv.size();
+  const int64_t nc = coarse_rows(H);
+  auto sz = [&](int64_t n) {
+    size_t b = sizeof(double) * (size_t)std::max<int64_t>(n, 1) * (size_t)k;
+    return (b + 255) & ~size_t(255);
+  };
+  size_t total = 0;
+  for (size_t l = 0; l < nl; ++l) total += (l > 0 ? 4 : 2) * sz(H->lv[l].n);
+  total += 3 * sz(nc);
+  if (nl == 0) total += sz(nc);
+  if (H->mv_bytes < total) {
+    if (H->mv_mem) (void)hipFree(H->mv_mem);  // ordered after every earlier use (cache semantics)
+    H->mv_mem = nullptr;
+    H->mv_bytes = 0;
+    MLAMG_HIP(hipMalloc(&H->mv_mem, total));
+    H->mv_bytes = total;
+  }
+  char* p = static_cast<char*>(H->mv_mem);
+  auto take = [&](int64_t n) {
+    double* q = reinterpret_cast<double*>(p);
+    p += sz(n);
+    return q;
+  };
+  W->lv.resize(nl);
+  for (size_t l = 0; l < nl; ++l) {
+    if (l > 0) {
+      W->lv[l].x = take(H->lv[l].n);
+      W->lv[l].b = take(H->lv[l].n);
+    }
+    W->lv[l].r = take(H->lv[l].n);
+    W->lv[l].tmp = take(H->lv[l].n);
+  }
+  W->xc = take(nc);
+  W->bc = take(nc);
+  W->yc = take(nc);
+  if (nl == 0) W->r0 = take(nc);
+  W->k = k;
+  return MLAMG_OK;
+}
+
+static int smooth_mv(const Level& L, const double* B, int64_t ldb, double*& cur, int64_t& lc,
+                     double*& other, int64_t& lo, int nu, int k, hipStream_t s) {
+  for (int i = 0; i < nu; ++i) {
+    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s));
+    std::swap(cur, other);
+    std::swap(lc, lo);
+  }
+  return MLAMG_OK;
+}
+
+// one V-cycle below the finest level from a zero guess (cycle_coarse); every block has ld = k
+static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, double** res,
+                           hipStream_t s) {
+  const int k = W.k;
+  if (l == H->lv.size()) {
+    MLAMG_TRY(dense_solve_mv(H->D, B, k, W.xc, k, k, W.yc, s));
+    *res = W.xc;
+    return MLAMG_OK;
+  }
+  const Level& L = H->lv[l];
+  MvLevel& M = W.lv[l];
+  double* cur = M.x;
+  double* other = M.tmp;
+  int64_t lc = k, lo = k;
+  const size_t bytes = sizeof(double) * (size_t)L.n * (size_t)k;
+  if (H->nu_pre > 0) {
+    MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s));
+    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s));
+    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s));
+  } else {
+    MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
+    MLAMG_HIP(hipMemcpyAsync(M.r, B, bytes, hipMemcpyDeviceToDevice, s));
+  }
+  double* bn = (l + 1 < H->lv.size()) ? W.lv[l + 1].b : W.bc;
+  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s));
+  double* xn = nullptr;
+  MLAMG_TRY(cycle_coarse_mv(H, W, l + 1, bn, &xn, s));
+  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s));
+  other = (cur == M.x) ? M.tmp : M.x;
+  MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_post, k, s));
+  *res = cur;
+  return MLAMG_OK;
+}
+}  // namespace
+
 extern "C" {
+
+int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
+                         int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
+                         void* stream) {
+  MLAMG_REQUIRE(H && X, "NULL argument");
+  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
+  MLAMG_REQUIRE(ldx >= k && (!B || ldb >= k), "leading dimension < k");
+  MLAMG_REQUIRE(B != X, "B and X must differ");
+  MLAMG_REQUIRE(n_cycles >= 0, "n_cycles < 0");
+  MLAMG_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode must be 0 (residual) or 1 (x)");
+  if (H->pcg) return mv_unsupported("the coarse solve is PCG (dense coarse solves only)");
+  if (H->gm_inner) return mv_unsupported("the coarse solve is GMRES (dense coarse solves only)");
+  for (const Level& L : H->lv) {
+    if (L.gs) return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)");
+    if (L.fac_A) return mv_unsupported("a level uses a factored prolongation");
+    if (L.A->vec_width || L.P->vec_width || L.R->vec_width)
+      return mv_unsupported("an operator is in the VECTOR format, whose row order is not scipy's");
+  }
+  MLAMG_TRY(hier_prepare(H));
+  hipStream_t s = S(stream);
+  MvWork W;
+  MLAMG_TRY(mv_workspace(H, k, &W));
+  if (H->lv.empty()) {  // coarse-only hierarchy: X = A^-1 B each cycle
+    const int64_t nc = H->D->n;
+    if (!B) {
+      MLAMG_HIP(hipMemsetAsync(W.bc, 0, sizeof(double) * (size_t)std::max<int64_t>(nc, 1) * k, s));
+      B = W.bc;
+      ldb = k;
+    }
+    if (hist && norm_mode == 0 && !H->Ac)
+      return mv_unsupported("a coarse-only hierarchy without its operator has no residual norm");
+    for (int c = 0; c < n_cycles; ++c) {
+      MLAMG_TRY(dense_solve_mv(H->D, B, ldb, X, ldx, k, W.yc, s));
+      if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, nc, k, s));
+      if (hist && norm_mode == 0) {
+        MLAMG_TRY(residual_mv(H->Ac, B, ldb, X, ldx, W.r0, k, k, s));
+        MLAMG_TRY(norm2_mv(W.r0, k, nc, k, hist + (int64_t)c * k, s));
+      } else if (hist) {
+        MLAMG_TRY(norm2_mv(X, ldx, nc, k, hist + (int64_t)c * k, s));
+      }
+    }
+    return MLAMG_OK;
+  }
+  const Level& L = H->lv[0];
+  MvLevel& M = W.lv[0];
+  bool have_r = false;  // M.r == B - A X (the end-of-cycle residual, reused by the next sweep)
+  for (int c = 0; c < n_cycles; ++c) {
+    double* cur = X;
+    double* other = M.tmp;
+    int64_t lc = ldx, lo = k;
+    if (!have_r) MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
+    if (H->nu_pre > 0) {
+      MLAMG_TRY(diag_mv(X, ldx, L.dinv, M.r, k, L.n, k, 0, s));
+      MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre - 1, k, s));
+      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s));
+    }
+    double* bn = H->lv.size() > 1 ? W.lv[1].b : W.bc;
+    MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s));
+    double* xn = nullptr;
+    MLAMG_TRY(cycle_coarse_mv(H, W, 1, bn, &xn, s));
+    MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, lc, k, s));
+    if (cur == X) {
+      other = M.tmp;
+      lo = k;
+    } else {
+      other = X;
+      lo = ldx;
+    }
+    MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_post, k, s));
+    if (cur != X && L.n > 0)
+      MLAMG_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, cur, sizeof(double) * lc,
+                                 sizeof(double) * k, L.n, hipMemcpyDeviceToDevice, s));
+    if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, L.n, k, s));
+    have_r = false;
+    if (hist && norm_mode == 0) {
+      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
+      MLAMG_TRY(norm2_mv(M.r, k, L.n, k, hist + (int64_t)c * k, s));
+      have_r = true;
+    } else if (hist) {
+      MLAMG_TRY(norm2_mv(X, ldx, L.n, k, hist + (int64_t)c * k, s));
+    }
+  }
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
 
 int mlamg_hier_create(mlamg_hier** out) {
   MLAMG_REQUIRE(out, "out is NULL");
@@ -400,6 +601,7 @@ int mlamg_hier_destroy(mlamg_hier* H) {
   if (H->done_host) (void)hipHostFree(H->done_host);
   if (H->ws) (void)hipFree(H->ws);
   if (H->zero_b) (void)hipFree(H->zero_b);
+  if (H->mv_mem) (void)hipFree(H->mv_mem);
   delete H;
   return MLAMG_OK;
 }

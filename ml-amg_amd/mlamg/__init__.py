@@ -11,6 +11,8 @@ Mirrors the reference modules on the hot path:
                                                   strength of connection on the device)
   mlamg.preconditioner  <- ns/preconditioner     (MLAMG PC: initialize/update/apply)
   mlamg.gnn             <- ns/model/agg_interp.py (FullAggNet inference: AggNet, MPNN)
+  mlamg.loss            <- ns/model/loss.py      (amg_loss forward evaluation on a block of
+                                                  test vectors, fp64)
   mlamg.hierarchy       multilevel device hierarchy + V-cycle executor (precondition/solve)
   mlamg.distributed     fine level row-partitioned over GPUs (RCCL halo exchange)
 
@@ -23,7 +25,7 @@ import importlib
 __version__ = "0.1.0"
 
 _SUBMODULES = ("multigrid", "graph", "sparse", "strength", "gnn", "hierarchy",
-               "preconditioner", "problems", "gridio", "distributed", "_lib")
+               "preconditioner", "problems", "gridio", "distributed", "loss", "_lib")
 
 
 def __getattr__(name):

@@ -183,6 +183,19 @@ SIGNATURES = {
     "mlamg_hier_vcycle": (c_int, [c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, P_i32, c_int, c_vp]),
     "mlamg_hier_cycle_bytes": (c_int, [c_vp, P_dbl]),
     "mlamg_hier_cycle_format_bytes": (c_int, [c_vp, P_dbl]),
+    # multi-vector (row-major n x k) path (csrc/spmm.hip, csrc/hier.hip)
+    "mlamg_spmm": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp]),
+    "mlamg_residual_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp,
+                                  c_vp]),
+    "mlamg_jacobi_mv": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_int,
+                                c_vp]),
+    "mlamg_restrict_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mlamg_prolong_add_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mlamg_norm2_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
+    "mlamg_remove_mean_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp]),
+    "mlamg_dense_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mlamg_hier_vcycle_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int,
+                                     c_vp, c_vp]),
     "mlamg_comm_unique_id": (c_int, [c_vp]),
     "mlamg_comm_create": (c_int, [c_vp, c_int, c_int, c_vpp]),
     "mlamg_comm_destroy": (c_int, [c_vp]),

@@ -1052,8 +1052,43 @@ class Hierarchy:
         k = min(1 if it == 0 else it + 1, cap)
         return x, {"info": info.value, "iters": it, "residuals": np.array(hist[:k])}
 
+    def cycle_multi(self, B, X, n_cycles, norm="residual", remove_mean=False, history=True):
+        """Run n_cycles V-cycles in place on the block X of k <= 64 vectors (cuda fp64 (n, k)
+        tensors with unit column stride; B=None: a zero right-hand side) through the
+        multi-vector kernels (mlamg_hier_vcycle_mv): every operator is streamed once for all k
+        columns, and column j has the bits of the single-vector cycle on column j.
+        remove_mean subtracts each column's mean after every cycle's post-smoothing
+        (ns/model/loss.py:89). Returns the (n_cycles, k) history (numpy) of ||b - A x||_2
+        (norm='residual') or ||x||_2 (norm='x') per column, taken after the mean removal; None
+        with history=False. A fixed cycle count, run eagerly; weighted-Jacobi levels with a
+        dense coarse solve only (MlamgError EUNSUPPORTED otherwise)."""
+        from .sparse import mv_block
+        if norm not in ("residual", "x"):
+            raise ValueError(f"unknown norm {norm!r}")
+        n = self.levels[0].A.shape[0] if self.levels else self.Ac.shape[0]
+        k, ldx = mv_block(X, n, "X")
+        ldb = 0
+        if B is not None:
+            kb, ldb = mv_block(B, n, "B")
+            if kb != k:
+                raise ValueError(f"B has {kb} columns, X has {k}")
+        hist = (torch.zeros((max(n_cycles, 1), k), dtype=torch.float64, device=X.device)
+                if history else None)
+        self._solve_call("mlamg_hier_vcycle_mv", self.handle, ptr(B), ldb, ptr(X), ldx, k,
+                         int(n_cycles), 0 if norm == "residual" else 1, int(bool(remove_mean)),
+                         ptr(hist), stream_ptr())
+        if not history:
+            return None
+        return hist[: int(n_cycles)].cpu().numpy()
+
     def precondition(self, b):
-        """One V-cycle from a zero guess: the action of the preconditioner on b."""
+        """One V-cycle from a zero guess: the action of the preconditioner on b (a vector, or
+        an (n, k) block of k <= 64 right-hand sides: one cycle on every column)."""
+        if getattr(b, "ndim", 1) == 2:
+            bd = to_device_vec(b)
+            xd = torch.zeros_like(bd)
+            self.cycle_multi(bd, xd, 1, history=False)
+            return xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
         bd = to_device_vec(b)
         xd = torch.zeros_like(bd)
         self.cycle(bd, xd, 1, history=False)

@@ -60,6 +60,30 @@ def _check_int32(shape, nnz):
                          "index range of the device CSR handle")
 
 
+MV_MAX = 64  # MLAMG_MV_MAX (include/mlamg.h): the widest block of vectors of the n x k path
+
+
+def mv_block(X, n, name="X"):
+    """(k, ld) of a multivector argument of the C-ABI (include/mlamg.h): a cuda fp64 (n, k)
+    tensor, row-major with unit column stride and a row stride ld >= k counted in doubles."""
+    if not isinstance(X, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if X.dtype != torch.float64 or not X.is_cuda:
+        raise TypeError(f"{name} must be a cuda float64 tensor")
+    if X.ndim != 2:
+        raise ValueError(f"{name} must be 2-D, got {X.ndim}-D")
+    if X.shape[0] != n:
+        raise ValueError(f"{name} has {X.shape[0]} rows, expected {n}")
+    k = int(X.shape[1])
+    if not 1 <= k <= MV_MAX:
+        raise ValueError(f"{name} has {k} columns; the block path takes 1 to {MV_MAX}")
+    ld = int(X.stride(0)) if n > 1 else max(int(X.stride(0)), k)
+    if X.stride(1) != 1 or ld < k:
+        raise ValueError(f"{name} must have unit column stride and a row stride >= its width "
+                         f"(strides {tuple(X.stride())})")
+    return k, ld
+
+
 class DeviceCSR:
     """An int32/fp64 CSR matrix resident on the GPU (owns a `mlamg_csr*`)."""
 
@@ -143,6 +167,20 @@ class DeviceCSR:
         call("mlamg_spmv", self.handle, ptr(x), ptr(out), alpha, beta, stream_ptr())
         return out
 
+    def matmat(self, X, out=None, alpha=1.0, beta=0.0):
+        """out = alpha * A @ X + beta * out on a block of k <= MV_MAX vectors (mlamg_spmm): X
+        is a cuda fp64 (n_cols, k) tensor with unit column stride — contiguous, or a column
+        slice of a wider tensor, used in place. Column j is bitwise matvec(X[:, j])."""
+        k, ldx = mv_block(X, self.shape[1], "X")
+        if out is None:
+            out = torch.zeros((self.shape[0], k), dtype=torch.float64, device=X.device)
+        ko, ldy = mv_block(out, self.shape[0], "out")
+        if ko != k:
+            raise ValueError(f"out has {ko} columns, X has {k}")
+        call("mlamg_spmm", self.handle, ptr(X), ldx, ptr(out), ldy, k, float(alpha), float(beta),
+             stream_ptr())
+        return out
+
     def transpose(self):
         h = ctypes.c_void_p()
         call("mlamg_transpose", self.handle, ctypes.byref(h), stream_ptr())
@@ -158,7 +196,7 @@ class DeviceCSR:
             call("mlamg_spgemm", self.handle, other.handle, ctypes.byref(h), stream_ptr())
             return DeviceCSR(h)
         if isinstance(other, torch.Tensor):
-            return self.matvec(other)
+            return self.matmat(other) if other.ndim == 2 else self.matvec(other)
         return NotImplemented
 
     FORMATS = {"csr_stream": 0, "sell": 1, "vector": 2, "auto_exact": 3, "sorted": 4,
