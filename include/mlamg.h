@@ -618,6 +618,24 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
                          int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
                          void* stream);
 
+/* Sampled dense-dense product on S's pattern (csrc/sddmm.hip; the gradient of amg_loss with
+ * respect to a prolongator's stored values, mlamg/loss.py):
+ *   out[e] = alpha * sum_{c<k} U[row(e), c] * V[col(e), c] + beta * out[e]
+ * for every stored entry e of S, in S's CSR entry order (out: nnz doubles; S's values are not
+ * read). U is n_rows x k and V is n_cols x k, multivectors as above (ldu, ldv >= k). With
+ * beta == 0 out is not read. The kernel reads S's CSR arrays and row-block table only, so it
+ * does not depend on the format active on the handle.
+ * SUMMATION ORDER, a fixed function of k: with G the smallest power of two >= ceil(k/2) and the
+ * columns k .. 2G-1 of U and V taken as +0.0,
+ *   t[p] = (U[i,2p] * V[j,2p]) + (U[i,2p+1] * V[j,2p+1]),  p = 0 .. G-1,
+ * then t[q] = t[2q] + t[2q+1] (q = 0 .. len/2-1) until one term s is left, and
+ *   out = alpha * s (beta == 0) or (alpha * s) + (beta * out),
+ * every multiply and add rounded on its own. It does not depend on the row-block partition, the
+ * entry's position in its row, ldu / ldv, pointer alignment or the (16-byte or 8-byte access)
+ * instantiation that ran. */
+int mlamg_sddmm(const mlamg_csr* S, const double* U, int64_t ldu, const double* V, int64_t ldv,
+                int k, double alpha, double beta, double* out, void* stream);
+
 /* ---------------------------------------------------------------- multi-GPU (RCCL over xGMI)
  * New relative to the reference, whose only parallelism is a process task farm over independent
  * grids (ns/parallel/pool.py:139-186, pickled objects over pipes / mpi4py, no collectives).

@@ -11,8 +11,8 @@ Mirrors the reference modules on the hot path:
                                                   strength of connection on the device)
   mlamg.preconditioner  <- ns/preconditioner     (MLAMG PC: initialize/update/apply)
   mlamg.gnn             <- ns/model/agg_interp.py (FullAggNet inference: AggNet, MPNN)
-  mlamg.loss            <- ns/model/loss.py      (amg_loss forward evaluation on a block of
-                                                  test vectors, fp64)
+  mlamg.loss            <- ns/model/loss.py      (amg_loss on a block of test vectors, fp64, and
+                                                  its gradient with respect to P's values)
   mlamg.hierarchy       multilevel device hierarchy + V-cycle executor (precondition/solve)
   mlamg.distributed     fine level row-partitioned over GPUs (RCCL halo exchange)
 

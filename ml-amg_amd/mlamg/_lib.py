@@ -196,6 +196,7 @@ SIGNATURES = {
     "mlamg_dense_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
     "mlamg_hier_vcycle_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int,
                                      c_vp, c_vp]),
+    "mlamg_sddmm": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp, c_vp]),
     "mlamg_comm_unique_id": (c_int, [c_vp]),
     "mlamg_comm_create": (c_int, [c_vp, c_int, c_int, c_vpp]),
     "mlamg_comm_destroy": (c_int, [c_vp]),

@@ -181,6 +181,29 @@ class DeviceCSR:
              stream_ptr())
         return out
 
+    def sddmm(self, U, V, alpha=1.0, beta=0.0, out=None):
+        """out[e] = alpha * (U[row(e), :] . V[col(e), :]) + beta * out[e] on every stored entry
+        e of this matrix, in CSR entry order (mlamg_sddmm: the sampled dense-dense product; the
+        stored values are not read). U: cuda fp64 (n_rows, k), V: (n_cols, k), k <= MV_MAX,
+        unit column stride (contiguous or column slices, used in place). Returns the length-nnz
+        cuda fp64 tensor; with beta == 0 `out` is overwritten without being read. The
+        summation order is fixed by k alone (include/mlamg.h)."""
+        k, ldu = mv_block(U, self.shape[0], "U")
+        kv, ldv = mv_block(V, self.shape[1], "V")
+        if kv != k:
+            raise ValueError(f"V has {kv} columns, U has {k}")
+        if out is None:
+            if beta != 0.0:
+                raise ValueError("beta != 0 needs an out tensor to accumulate into")
+            out = torch.empty(self.nnz, dtype=torch.float64, device=U.device)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or not out.is_cuda
+              or out.ndim != 1 or out.numel() != self.nnz or not out.is_contiguous()):
+            raise TypeError(f"out must be a contiguous cuda float64 tensor of length {self.nnz}")
+        if self.nnz:
+            call("mlamg_sddmm", self.handle, ptr(U), ldu, ptr(V), ldv, k, float(alpha),
+                 float(beta), ptr(out), stream_ptr())
+        return out
+
     def transpose(self):
         h = ctypes.c_void_p()
         call("mlamg_transpose", self.handle, ctypes.byref(h), stream_ptr())
