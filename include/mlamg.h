@@ -86,7 +86,8 @@ int mlamg_csr_download(const mlamg_csr* A, int32_t* indptr_host, int32_t* indice
  * per-entry hashes; keys the format autotune's cache, no reference counterpart); syncs */
 int mlamg_csr_fingerprint(const mlamg_csr* A, uint64_t* fp_host, void* stream);
 
-/* SpMV storage/kernel of a handle (the CSR arrays always stay; formats add a device copy):
+/* SpMV storage/kernel of a handle (the CSR arrays always stay; formats add a device copy; a
+ * conversion that is refused or fails leaves the handle in the format it had):
  *   CSR_STREAM  LDS-staged row blocks, lane-per-row sums in stored order (scipy's bits)
  *   SELL        SELL-64 slices, lane-per-row sums in stored order (scipy's bits); vec_width > 1
  *               is read as sigma: rows sorted by length inside windows of sigma rows
@@ -112,7 +113,7 @@ int mlamg_csr_fingerprint(const mlamg_csr* A, uint64_t* fp_host, void* stream);
  *             patterns): lossless, same products in the same order as SELL (scipy's bits).
  *             For constant-coefficient stencils (C4: 7 offsets, 2 values) the matrix stream is
  *             2 B/nonzero instead of 12. vec_width = sigma as for SELL. EUNSUPPORTED (format
- *             reset to CSR_STREAM) when the dictionaries overflow. */
+ *             unchanged) when the dictionaries overflow. */
 #define MLAMG_FMT_SELL_DICT 5
 /* ROWPAT      every row is one of <= 255 distinct patterns (its (col - row, value) sequence in
  *             stored order; C4's 7-point Laplacian: 27 interior/face/edge/corner patterns) held

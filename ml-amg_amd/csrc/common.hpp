@@ -94,6 +94,8 @@ constexpr double kSrtLongRow = MLAMG_SRT_LONG_ROW;
 constexpr int kLongNnz = 4096;
 constexpr int kLongRows = 64;
 
+// Row-pair patterns: padded entries of all patterns together, at most (LDS tables of k_rowpair)
+constexpr int kRpMaxEnt = 2048;
 // Row-pair pattern LDS windows (spmv.hip k_rowpair_win): cluster k of the wide entries' offsets
 // is staged as rows [R0 + s[k], R0 + s[k] + len[k]) of x at window row base[k]
 constexpr int kRpWinMax = 4;
@@ -124,7 +126,7 @@ struct RpUni {
   double v1[kRpUniMax] = {0, 0, 0, 0, 0, 0, 0, 0};     // row 2i+1's
   // far slot t (in slot order) reads x at pair offset alt_off[t] instead of its own offset for
   // the pairs [alt_lo[t], alt_hi[t]) — a row-partitioned slab's ghost plane (its x_ext position
-  // is not the plane's global offset; build_rowpat). Empty range: none.
+  // is not the plane's global offset; formats.hip build_rowpat). Empty range: none.
   int32_t alt_off[kRpUniFar] = {0, 0};
   int32_t alt_lo[kRpUniFar] = {0, 0};
   int32_t alt_hi[kRpUniFar] = {0, 0};

@@ -13,7 +13,7 @@
 // x = Dinv_w b (0 + d*(b - A@0) bit for bit). The tolerance test runs on the device: the norm
 // kernel raises a flag and every later kernel of the call returns immediately, so a whole batch
 // of cycles is launched (or replayed from one captured hipGraph) without host round trips.
-#include "common.hpp"
+#include "formats.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -715,7 +715,7 @@ int mlamg_hier_set_factored_prolong(mlamg_hier* H, int level, const mlamg_csr* A
   }
   MLAMG_REQUIRE(agg && dinv_w, "agg and dinv_w are required");
   MLAMG_REQUIRE(A_uni->n_rows == L.n && A_uni->n_cols == L.n, "A_uni is not this level's size");
-  if (!(A_uni->rp_pid && A_uni->rp_uni.k > 0 && A_uni->rp_msk)) {
+  if (!rowpat_uniform(A_uni)) {
     set_error("factored prolongation: A_uni is not in the uniform row-pair format");
     return MLAMG_EUNSUPPORTED;
   }

@@ -1,6 +1,6 @@
 // Runtime pieces of libmlamg_hip: error state, device CSR handle lifecycle, CSR-stream
 // partitioning, scratch buffers. Host C++ compiled by hipcc; no torch dependency.
-#include "common.hpp"
+#include "formats.hpp"
 
 #include <atomic>
 
@@ -221,31 +221,7 @@ void csr_free(mlamg_csr* A) {
     if (A->data) (void)hipFree(A->data);
   }
   if (A->blk) (void)hipFree(A->blk);
-  if (A->sell_ptr) (void)hipFree(A->sell_ptr);
-  if (A->sell_col) (void)hipFree(A->sell_col);
-  if (A->sell_val) (void)hipFree(A->sell_val);
-  if (A->sell_perm) (void)hipFree(A->sell_perm);
-  if (A->dict_code) (void)hipFree(A->dict_code);
-  if (A->dict_ptr) (void)hipFree(A->dict_ptr);
-  if (A->dict_off) (void)hipFree(A->dict_off);
-  if (A->dict_val) (void)hipFree(A->dict_val);
-  if (A->srt_blk) (void)hipFree(A->srt_blk);
-  if (A->srt_base) (void)hipFree(A->srt_base);
-  if (A->srt_pk) (void)hipFree(A->srt_pk);
-  if (A->srt_val) (void)hipFree(A->srt_val);
-  if (A->srt_vi) (void)hipFree(A->srt_vi);
-  if (A->srt_vtab) (void)hipFree(A->srt_vtab);
-  if (A->srt_vc) (void)hipFree(A->srt_vc);
-  if (A->srt_vblk) (void)hipFree(A->srt_vblk);
-  if (A->vec_idx16) (void)hipFree(A->vec_idx16);
-  if (A->rp_pid) (void)hipFree(A->rp_pid);
-  if (A->rp_ptr) (void)hipFree(A->rp_ptr);
-  if (A->rp_off) (void)hipFree(A->rp_off);
-  if (A->rp_val) (void)hipFree(A->rp_val);
-  if (A->rp_dinv) (void)hipFree(A->rp_dinv);
-  if (A->rp_slot) (void)hipFree(A->rp_slot);
-  if (A->rp_msk) (void)hipFree(A->rp_msk);
-  if (A->lg_tile) (void)hipFree(A->lg_tile);
+  drop_formats(A);
   delete A;
 }
 

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build an A/B variant of libmlamg_hip.so with extra -D flags on one source (default spmv.hip;
 # SRC=batch.hip for another, SRC_PATH=<file> to compile a different copy of it); the other
-# objects are the in-tree build's. Timing runs pick it with MLAMG_LIB=<out>:
+# objects are the in-tree build's. Knobs of the format builders need SRC=formats.hip.
+# Timing runs pick it with MLAMG_LIB=<out>:
 #   tools/build_variant.sh tools/variants/libmlamg_w6.so -DMLAMG_RP_WAVES=6
 set -eu
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
