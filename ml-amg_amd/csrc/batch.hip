@@ -26,82 +26,30 @@
 // every matrix the cycles read is pre-packed into fixed-width slot-major rows (all loads of a
 // phase independent: one round trip per phase), the sweep's rows are staged into LDS a chunk of
 // levels at a time, and the pivot search of Gauss-Jordan step k+1 rides on step k's barrier.
-// Structure-only preparation (level schedule, transposed sparsity of P, packing) is done on the
-// host from the CSR index arrays the caller hands over; every floating-point operation runs in
-// the kernel.
+// Structure-only preparation (level schedule, transposed sparsity of P, packing), the choice of
+// kernel variant per problem and the arena layout are the host planner's (batch_plan.cpp: host-only
+// code working on the CSR index arrays the caller hands over; batch_plan.hpp holds the limits, the
+// descriptor and the LDS sizes that planner and kernels share). Every floating-point operation
+// runs in the kernels here.
 #include "common.hpp"
 
-#include <sched.h>
-#include <unistd.h>
-
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <memory>
-#include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
+
+#include "batch_plan.hpp"
 
 namespace mlamg {
 namespace {
 
-constexpr int kBT = 1024;
 constexpr int kBWaves = kBT / 64;
-constexpr int64_t kBMaxN = 16384;   // fine rows: x lives in LDS during the cycles
-constexpr int64_t kBMaxNc = 2048;   // coarse rows: dense inverse, LDS panels of >= 4 columns
-constexpr int kBMaxK = 32;          // off-diagonal entries per row of A
-constexpr int kBMaxKP = 32;         // entries per row of P
-constexpr int kBMaxKT = 256;        // entries per row of P^T
-constexpr int kBMaxPanel = 16;
 #ifndef MLAMG_GS_SCHED_FENCE  // build-time A/B knob: scheduling barrier after a level's stores
 #define MLAMG_GS_SCHED_FENCE 1
 #endif
-constexpr int kExtCoarseMin = 300;  // single calls above this n_c: device-wide coarse factor
-constexpr size_t kBLdsBytes = 156 * 1024;
-
-struct BDesc {
-  int32_t n, nc, smoother, nu_pre, nu_post, norm_mode, max_iter;
-  int32_t K, KA, KP, KT, nlev, panel, n_chunks, cap, timing;
-  int32_t spd;    // A symmetric: try the inverse Cholesky factor before Gauss-Jordan
-  int32_t chol_nb;  // its panel width (4..16, from n_c)
-  int32_t setup_mode;  // 0: Galerkin + coarse inverse here; 1: neither (k_galerkin_rows and the
-                       // device-wide factorisation of dense.hip); 2: Galerkin only (the batched
-                       // device-wide factorisation follows); 3: nothing (a relaunch's bystander)
-  int32_t gs_rw;  // one-wave sweep (rows of K = 4 or 8 slots, levels <= 64 * gs_rw rows), 1 or 2
-                  // rows per lane; 0: the workgroup sweeps each level
-  int32_t gs_db;   // one-wave sweep: double-buffered chunk staging (chunks of >= 3 levels)
-  int32_t gs_rp;   // one-wave sweep, one buffer: the next chunk prefetched into registers
-  int32_t phased;  // single large problem: each cycle is two launches, the workgroup's half
-                   // cycles and the coarse solve on every CU (k_amg2v_coarse); r_H, e_H global
-  double tol, omega;
-  // byte offsets into the arena; packed arrays are slot-major: a[s * rows + row]
-  int64_t ak_col, ak_val;                  // A rows, stored order incl. diagonal (KA slots)
-  int64_t pp_col, pp_val;                  // P rows (KP slots)
-  int64_t pt_row, pt_val;                  // P^T rows: fine rows ascending (KT slots)
-  int64_t lev_ptr, chunk_lev, pk_row, pk_col, pk_val, pk_diag, b_lvl;  // sweep, level order
-  int64_t b, x0;
-  int64_t AH, AI, rg, dinv;                // Galerkin / un-pivoted inverse / r when not in
-                                           // LDS / weighted-Jacobi weights
-  int64_t x_out, err_out, stat_out;
-  int64_t rcg, eg, yg;  // phased: r_H, e_H and L^-1 r_H in the arena
-  int64_t done_ctr;     // phased: problems finished (one counter for the launch)
-  // the problem's values as the caller stores them (A.data, P.data) and its shape's gather maps
-  // (shared by every problem with the same sparsity): the packed value arrays above are
-  // gathered from them on the device (gather_values), so only the caller's values travel
-  int64_t a_raw, p_raw;
-  int64_t a_map, p_map, t_map, g_map, d_map, pk_row0;
-  // banded coarse solve (band_ld = half-bandwidth + 1, 0: dense): the factor in the band
-  // solve's lane layouts F (forward) and G (backward), reciprocal diagonal
-  int32_t band_ld, pad0;
-  int64_t lc, lr, rinv;
-};
 
 template <class T>
 __device__ __forceinline__ T* at(char* base, int64_t off) {
@@ -564,12 +512,6 @@ __device__ void gather_values(const BDesc& D, char* arena, int tid) {
 // n_c^3 / 3 + ...) and two band substitutions per cycle (4 n_c b bytes instead of 8 n_c^2).
 // Held, like the dense paths, to fp64 rounding of a direct solve; chosen per problem from its own
 // pattern, so a problem's results do not depend on its batch.
-constexpr int kBandMax = 63;  // half-bandwidth limit: rows (j, j + b] within the 64 lanes
-// coarse size limit: the substitutions run on one wave, ~45 ns per row and direction; a single
-// call with a larger coarse operator is faster with the device-wide dense factor and its coarse
-// solve spread over the CUs (128^2: 13 vs 26 ms). Every batch-eligible size (n_c <= 1024, the
-// Python engine's FUSED_BATCH_MAX_NC) is below it, so batches and single calls choose alike.
-constexpr int kBandMaxNc = 1024;
 
 __device__ __forceinline__ double readlane_d(double v, int l) {
   const long long x = __double_as_longlong(v);
@@ -596,7 +538,6 @@ using as_cptr = const __attribute__((address_space(AS))) double*;
 // padded by kBandPad zero steps on either side, see band_solve): F[j][i mod 64] = L[i][j] / L[j][j]
 // for i in (j, j + b], G[i][j mod 64] = L[i][j], RI[j] = 1 / L[j][j]. Returns false
 // (uniformly) on a non-positive pivot.
-constexpr int kBandPad = 32;  // zero steps before and after the band solve's lane layout
 __device__ __forceinline__ int64_t band_at(int j, int l) { return (int64_t)(j + kBandPad) * 64 + l; }
 
 // LDS ordering between the lanes of one wave: its LDS operations complete in issue order, so a
@@ -1723,15 +1664,6 @@ __global__ __launch_bounds__(kBT) void k_amg2v_cycles(const BDesc* __restrict__ 
   }
 }
 
-struct Layout {
-  size_t off = 0;
-  int64_t take(size_t bytes) {
-    const int64_t o = (int64_t)off;
-    off += (std::max<size_t>(bytes, 1) + 255) & ~size_t(255);
-    return o;
-  }
-};
-
 struct HostPinned {
   void* p = nullptr;
   size_t cap = 0;
@@ -1741,539 +1673,201 @@ struct HostPinned {
 };
 thread_local HostPinned g_batch_host;
 
-bool valid_csr(int64_t rows, int64_t cols, int64_t nnz, const int32_t* ip, const int32_t* ij) {
-  if (!ip || (nnz > 0 && !ij) || ip[0] != 0 || ip[rows] != nnz) return false;
-  for (int64_t i = 0; i < rows; ++i)
-    if (ip[i + 1] < ip[i]) return false;
-  for (int64_t k = 0; k < nnz; ++k)
-    if (ij[k] < 0 || ij[k] >= cols) return false;
-  return true;
+// the pinned staging buffer, grown geometrically: batches of similar size reuse it
+int pinned_buffer(size_t need, char** out) {
+  HostPinned& H = g_batch_host;
+  if (H.cap < need) {
+    if (H.p) (void)hipHostFree(H.p);
+    H.p = nullptr;
+    H.cap = 0;
+    const size_t grow = need + need / 2;
+    MLAMG_HIP(hipHostMalloc(&H.p, grow, hipHostMallocDefault));
+    H.cap = grow;
+  }
+  *out = static_cast<char*>(H.p);
+  return MLAMG_OK;
 }
 
-// A == A^T exactly (values included): then A_H = P^T A P is symmetric and, A being SPD, the
-// coarse solve can take the inverse Cholesky factor
-bool csr_symmetric(int64_t n, const int32_t* ip, const int32_t* ij, const double* v) {
-  const int64_t nnz = ip[n];
-  std::vector<int32_t> tp(n + 1, 0), ti(nnz);
-  std::vector<double> tv(nnz);
-  for (int64_t k = 0; k < nnz; ++k) tp[ij[k] + 1]++;
-  for (int64_t j = 0; j < n; ++j) tp[j + 1] += tp[j];
-  std::vector<int32_t> fill(tp.begin(), tp.end() - 1);
-  for (int64_t i = 0; i < n; ++i)
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) {
-      ti[fill[ij[k]]] = (int32_t)i;
-      tv[fill[ij[k]]++] = v[k];
-    }
-  // row i of A^T lists its columns ascending; compare with row i of A sorted by column
-  std::vector<std::pair<int32_t, double>> row;
-  for (int64_t i = 0; i < n; ++i) {
-    if (ip[i + 1] - ip[i] != tp[i + 1] - tp[i]) return false;
-    row.clear();
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) row.emplace_back(ij[k], v[k]);
-    std::sort(row.begin(), row.end(),
-              [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) {
-                return a.first < b.first;
-              });
-    for (size_t q = 0; q < row.size(); ++q)
-      if (row[q].first != ti[tp[i] + q] || !(row[q].second == tv[tp[i] + q])) return false;
+struct Launch {  // what every launch of a call shares
+  const BatchPlan& plan;
+  char* hb;     // host copy of the arena's input part (descriptors first)
+  char* arena;  // device
+  hipStream_t s;
+  unsigned count() const { return (unsigned)plan.desc.size(); }
+  const BDesc* dd() const { return reinterpret_cast<const BDesc*>(arena + plan.desc_off); }
+  void setup(unsigned blocks, int pass) const {
+    hipLaunchKernelGGL(k_amg2v_setup, dim3(blocks), dim3(kBT), plan.lds_setup, s, dd(), arena,
+                       pass);
   }
-  return true;
-}
-
-// f(0 .. count-1) on up to MLAMG_HOST_THREADS (default: the CPUs this process may run on, at
-// most 16) host threads; the calling thread takes a share. Small counts run inline.
-// Persistent host workers for parallel_for (creating and joining 15 threads per call cost
-// ~0.5 ms of a 48-grid batch). One job at a time; a caller that finds the pool busy (another
-// host thread's batch) runs its loop inline.
-class HostPool {
- public:
-  explicit HostPool(int workers) {
-    for (int t = 0; t < workers; ++t) th_.emplace_back([this] { loop(); });
-  }
-  ~HostPool() {
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      stop_ = true;
-    }
-    cv_.notify_all();
-    for (auto& t : th_) t.join();
-  }
-  int workers() const { return (int)th_.size(); }
-  // f(0 .. count-1) on the workers and the calling thread; false when the pool is busy
-  bool run(int count, const std::function<void(int)>& f) {
-    if (getpid() != pid_) return false;  // a forked child has no workers
-    std::unique_lock<std::mutex> busy(run_mu_, std::try_to_lock);
-    if (!busy.owns_lock()) return false;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      job_ = &f;
-      count_ = count;
-      next_.store(0);
-      active_ = (int)th_.size();
-      ++gen_;
-    }
-    cv_.notify_all();
-    for (int q = next_.fetch_add(1); q < count; q = next_.fetch_add(1)) f(q);
-    std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [this] { return active_ == 0; });
-    job_ = nullptr;
-    return true;
-  }
-
- private:
-  void loop() {
-    uint64_t seen = 0;
-    for (;;) {
-      const std::function<void(int)>* job;
-      int count;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
-        if (stop_) return;
-        seen = gen_;
-        job = job_;
-        count = count_;
-      }
-      for (int q = next_.fetch_add(1); q < count; q = next_.fetch_add(1)) (*job)(q);
-      std::lock_guard<std::mutex> lk(mu_);
-      if (--active_ == 0) done_cv_.notify_all();
-    }
-  }
-  std::vector<std::thread> th_;
-  std::mutex mu_, run_mu_;
-  std::condition_variable cv_, done_cv_;
-  const std::function<void(int)>* job_ = nullptr;
-  int count_ = 0, active_ = 0;
-  uint64_t gen_ = 0;
-  std::atomic<int> next_{0};
-  bool stop_ = false;
-  pid_t pid_ = getpid();
 };
 
-int host_threads() {
-  static const int max_threads = [] {
-    int t = 16;
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) t = std::min(t, CPU_COUNT(&set));
-    if (const char* e = std::getenv("MLAMG_HOST_THREADS")) t = std::max(1, std::atoi(e));
-    return std::max(1, t);
-  }();
-  return max_threads;
-}
-
-HostPool& host_pool() {  // one pool for every parallel_for of the process
-  static HostPool pool(host_threads() - 1);
-  return pool;
-}
-
+// A device-wide factor failed: the setup kernel's Gauss-Jordan for the problems `patch` marked
+// in the first `blocks` descriptors of the host copy
 template <class F>
-void parallel_for(int count, F&& f) {
-  if (host_threads() <= 1 || count < 4) {
-    for (int q = 0; q < count; ++q) f(q);
-    return;
-  }
-  const std::function<void(int)> fn = [&](int q) { f(q); };
-  if (!host_pool().run(count, fn))
-    for (int q = 0; q < count; ++q) f(q);
+int refactor_in_setup(const Launch& L, unsigned blocks, F&& patch) {
+  patch(reinterpret_cast<BDesc*>(L.hb + L.plan.desc_off));
+  MLAMG_HIP(hipMemcpyAsync(L.arena + L.plan.desc_off, L.hb + L.plan.desc_off,
+                           sizeof(BDesc) * blocks, hipMemcpyHostToDevice, L.s));
+  MLAMG_HIP(hipStreamSynchronize(L.s));
+  L.setup(blocks, 0);
+  return MLAMG_OK;
 }
 
-// ---------------------------------------------------------------- problem patterns and shapes
-// Everything the host derives from a problem's index arrays alone is computed once per distinct
-// sparsity pattern and kept across calls (a dataset's grids share few patterns: the reference's
-// farms loop over grids of a handful of sizes); per problem only the caller's values travel
-// (A.data, P.data, b, x0) and are placed into the packed layouts on the device.
-//   Pattern: the arrays (for the exact match), the exact-symmetry pairing of A's entries and the
-//            half-bandwidth of A_H = P^T A P — independent of the batch's flags;
-//   Shape:   a pattern's level schedule, packed column layouts and value maps for one set of
-//            batch flags (smoother, phased, residual in LDS, single call).
-struct Pattern {
-  int64_t n = 0, nc = 0, annz = 0, pnnz = 0;
-  uint64_t key = 0;
-  std::vector<int32_t> aip, aij, pip, pij;
-  // sym[k] = index of entry (j, i) for entry k = (i, j); sym_ok false when an entry has no
-  // mirror; dups when a row repeats a column (the value test then sorts, csr_symmetric)
-  std::vector<int32_t> sym;
-  bool sym_ok = false, dups = false;
-  int band = 0;  // half-bandwidth of A_H's structure (lower part)
-  size_t bytes() const { return 4 * (aip.size() + aij.size() + pip.size() + pij.size() + sym.size()); }
+// Galerkin products, value gathers and coarse factors
+int launch_setup(const Launch& L) {
+  const BatchPlan& plan = L.plan;
+  const std::vector<BDesc>& desc = plan.desc;
+  const int count = (int)L.count();
+  L.setup(L.count(), 0);
+  if (plan.any_band) {  // band factors, then Gauss-Jordan for any that met a non-positive pivot
+    hipLaunchKernelGGL(k_amg2v_band, dim3(L.count()), dim3(kBT), plan.lds_band, L.s, L.dd(),
+                       L.arena);
+    L.setup(L.count(), 1);
+  }
+  if (plan.ext_coarse) {
+    const BDesc& D = desc[0];
+    const int nc = D.nc;
+    const int R = std::max(1, std::min(64, (int)((size_t)128 * 1024 / (8 * (size_t)nc))));
+    hipLaunchKernelGGL(k_galerkin_rows, dim3((unsigned)((nc + R - 1) / R)), dim3(256),
+                       (size_t)R * nc * 8, L.s, L.dd(), L.arena, R);
+    // a single call with a large SPD coarse operator: the device-wide inverse Cholesky factor
+    // (all CUs) instead of one workgroup's; Gauss-Jordan in the setup kernel when not SPD
+    bool spd = false;
+    MLAMG_TRY(dense_chol_inverse(reinterpret_cast<double*>(L.arena + D.AH), D.nc,
+                                 reinterpret_cast<double*>(L.arena + D.AI), &spd, L.s));
+    if (!spd)
+      MLAMG_TRY(refactor_in_setup(L, 1, [](BDesc* Dh) {
+        Dh[0].setup_mode = 0;
+        Dh[0].spd = 0;
+      }));
+  }
+  if (plan.batch_ext) {
+    std::vector<DenseJob> jobs;
+    std::vector<int> who;
+    for (int q = 0; q < count; ++q)
+      if (desc[q].setup_mode == 2) {
+        DenseJob J{};
+        J.M = reinterpret_cast<double*>(L.arena + desc[q].AH);
+        J.inv = reinterpret_cast<double*>(L.arena + desc[q].AI);
+        J.n = desc[q].nc;
+        jobs.push_back(J);
+        who.push_back(q);
+      }
+    std::unique_ptr<bool[]> ok(new bool[std::max<size_t>(jobs.size(), 1)]);
+    MLAMG_TRY(dense_chol_inverse_batch(jobs.data(), (int)jobs.size(), ok.get(), L.s));
+    bool any_failed = false;
+    for (size_t j = 0; j < jobs.size(); ++j) any_failed = any_failed || !ok[j];
+    if (any_failed)  // Gauss-Jordan in the setup kernel for those, the others untouched
+      MLAMG_TRY(refactor_in_setup(L, L.count(), [&](BDesc* Dh) {
+        for (int q = 0; q < count; ++q) Dh[q].setup_mode = 3;
+        for (size_t j = 0; j < jobs.size(); ++j)
+          if (!ok[j]) {
+            Dh[who[j]].setup_mode = 0;
+            Dh[who[j]].spd = 0;
+          }
+      }));
+  }
+  return MLAMG_OK;
+}
+
+// k_amg2v_cycles<residual in LDS, phased, register prefetch>; the prefetch exists as a phased
+// variant only (plan.rp implies plan.phased)
+template <bool PHASED>
+void launch_cycle_kernel(const Launch& L) {
+  const BatchPlan& plan = L.plan;
+  const dim3 grid(L.count()), block(kBT);
+  if (plan.r_lds && plan.rp)
+    hipLaunchKernelGGL((k_amg2v_cycles<true, PHASED, PHASED>), grid, block, plan.lds_cycles, L.s,
+                       L.dd(), L.arena);
+  else if (plan.r_lds)
+    hipLaunchKernelGGL((k_amg2v_cycles<true, PHASED, false>), grid, block, plan.lds_cycles, L.s,
+                       L.dd(), L.arena);
+  else if (plan.rp)
+    hipLaunchKernelGGL((k_amg2v_cycles<false, PHASED, PHASED>), grid, block, plan.lds_cycles, L.s,
+                       L.dd(), L.arena);
+  else
+    hipLaunchKernelGGL((k_amg2v_cycles<false, PHASED, false>), grid, block, plan.lds_cycles, L.s,
+                       L.dd(), L.arena);
+}
+
+// per host thread: two pinned done-count slots and their events (freed at thread exit)
+struct PhaseFlags {
+  int32_t* host = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  ~PhaseFlags() {
+    for (auto e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (host) (void)hipHostFree(host);
+  }
 };
 
-struct Shape {
-  std::shared_ptr<const Pattern> pat;
-  int smoother = 0, phased = 0, r_lds = 0, single = 0;
-  // slot-major packed columns (-1 pads) and, per slot, the index of its value in A.data /
-  // P.data (-1: pad, value 0.0)
-  std::vector<int32_t> akc, amap, ppc, pmap, ptc, tmap;
-  // Gauss-Seidel sweep in level order: lev/clev (level and chunk starts), pkc/gmap the
-  // off-diagonal slots (position-major for the one-wave sweep), dmap the last stored diagonal
-  // entry of each position (-1: none), pkr0 the position's row
-  std::vector<int32_t> lev, clev, pkc, gmap, dmap, pkr0;
-  bool chol_fits = false;
-  int K = 1, KA = 1, KP = 1, KT = 1, nlev = 0, panel = 8, cap = 0, chol_nb = 4;
-  int gs_rw = 0, gs_db = 0, gs_rp = 0;
-  size_t lds_base = 0, lds_chol = 0, lds_cycles = 0;
-  int code = MLAMG_OK;
-  std::string err;
-  size_t bytes() const {
-    size_t b = 0;
-    for (const auto* v : {&akc, &amap, &ppc, &pmap, &ptc, &tmap, &lev, &clev, &pkc, &gmap, &dmap,
-                          &pkr0})
-      b += 4 * v->size();
-    return b;
+// Every cycle in one launch, or phased: cycle k = launches A_k (second half of cycle k - 1, first
+// half of cycle k) and B_k (the coarse solve); A_max_iter ends it. Every launch after the one
+// that met the tolerance returns at once; with a tolerance the host queues batches of cycles and
+// reads the done flag of the batch before the one it just queued, so the GPU never waits for the
+// host.
+int launch_cycles(const Launch& L, double tol, int max_iter) {
+  const BatchPlan& plan = L.plan;
+  if (!plan.phased) {  // rp is a phased variant: false here
+    launch_cycle_kernel<false>(L);
+    return MLAMG_OK;
   }
-};
-
-uint64_t mix_bytes(const void* data, size_t bytes, uint64_t h) {
-  const unsigned char* p = static_cast<const unsigned char*>(data);
-  constexpr uint64_t M1 = 0x9E3779B97F4A7C15ull, M2 = 0xC2B2AE3D27D4EB4Full;
-  uint64_t a = h ^ M1, b = h + M2, c = h * M1 + 1, d = h ^ M2;
-  size_t i = 0;
-  for (; i + 32 <= bytes; i += 32) {  // four independent lanes
-    uint64_t w[4];
-    std::memcpy(w, p + i, 32);
-    a = (a ^ w[0]) * M1;
-    b = (b ^ w[1]) * M2;
-    c = (c ^ w[2]) * M1;
-    d = (d ^ w[3]) * M2;
-    a ^= a >> 29;
-    b ^= b >> 31;
-    c ^= c >> 27;
-    d ^= d >> 33;
+  const int count = (int)L.count();
+  hipStream_t s = L.s;
+  const unsigned coarse_blocks = (unsigned)plan.cblk[count];
+  const int32_t* cb = reinterpret_cast<const int32_t*>(L.arena + plan.cblk_off);
+  MLAMG_HIP(hipMemsetAsync(L.arena + plan.done_off, 0, sizeof(int32_t), s));
+  const int total_a = max_iter + 1;
+  static thread_local PhaseFlags pf;
+  if (!pf.host) {
+    MLAMG_HIP(hipHostMalloc(&pf.host, 2 * sizeof(int32_t), hipHostMallocDefault));
+    for (auto& e : pf.ev) MLAMG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   }
-  for (; i < bytes; ++i) a = (a ^ p[i]) * M1;
-  uint64_t r = a ^ (b * M1) ^ (c * M2) ^ (d + M1) ^ bytes;
-  r ^= r >> 32;
-  return r * M2;
-}
-
-uint64_t pattern_key(const mlamg_amg2v_problem& P) {
-  int64_t hdr[4] = {P.n, P.n_c, P.A_nnz, P.P_nnz};
-  uint64_t h = mix_bytes(hdr, sizeof(hdr), 0x5A17u);
-  h = mix_bytes(P.A_indptr, 4 * (size_t)(P.n + 1), h);
-  h = mix_bytes(P.A_indices, 4 * (size_t)P.A_nnz, h);
-  h = mix_bytes(P.P_indptr, 4 * (size_t)(P.n + 1), h);
-  return mix_bytes(P.P_indices, 4 * (size_t)P.P_nnz, h);
-}
-
-bool same_pattern(const mlamg_amg2v_problem& a, const mlamg_amg2v_problem& b) {
-  if (a.n != b.n || a.n_c != b.n_c || a.A_nnz != b.A_nnz || a.P_nnz != b.P_nnz) return false;
-  auto eq = [](const int32_t* x, const int32_t* y, int64_t cnt) {
-    return x == y || cnt == 0 || std::memcmp(x, y, 4 * (size_t)cnt) == 0;
-  };
-  return eq(a.A_indptr, b.A_indptr, a.n + 1) && eq(a.A_indices, b.A_indices, a.A_nnz) &&
-         eq(a.P_indptr, b.P_indptr, a.n + 1) && eq(a.P_indices, b.P_indices, a.P_nnz);
-}
-
-bool pattern_matches(const Pattern& S, const mlamg_amg2v_problem& P) {
-  mlamg_amg2v_problem q{};
-  q.n = S.n;
-  q.n_c = S.nc;
-  q.A_nnz = S.annz;
-  q.P_nnz = S.pnnz;
-  q.A_indptr = S.aip.data();
-  q.A_indices = S.aij.data();
-  q.P_indptr = S.pip.data();
-  q.P_indices = S.pij.data();
-  return same_pattern(q, P);
-}
-
-// bounded most-recently-used lists (count and bytes); one lock for both
-std::mutex g_shape_mu;
-std::vector<std::shared_ptr<const Pattern>> g_patterns;
-std::vector<std::shared_ptr<const Shape>> g_shapes;
-constexpr size_t kCacheCount = 64;
-constexpr size_t kCacheBytes = size_t(256) << 20;
-
-template <class T>
-void cache_trim(std::vector<std::shared_ptr<const T>>& v) {
-  size_t total = 0;
-  for (const auto& t : v) total += t->bytes();
-  while (v.size() > 1 && (v.size() > kCacheCount || total > kCacheBytes)) {
-    total -= v.front()->bytes();
-    v.erase(v.begin());
-  }
-}
-
-std::shared_ptr<const Pattern> pattern_lookup(uint64_t key, const mlamg_amg2v_problem& P) {
-  std::lock_guard<std::mutex> lk(g_shape_mu);
-  for (size_t i = g_patterns.size(); i-- > 0;)
-    if (g_patterns[i]->key == key && pattern_matches(*g_patterns[i], P)) {
-      auto s = g_patterns[i];
-      g_patterns.erase(g_patterns.begin() + (long)i);
-      g_patterns.push_back(s);
-      return s;
-    }
-  return nullptr;
-}
-
-std::shared_ptr<const Shape> shape_lookup(const Pattern* pat, int smoother, int phased,
-                                          int r_lds, int single) {
-  std::lock_guard<std::mutex> lk(g_shape_mu);
-  for (size_t i = g_shapes.size(); i-- > 0;) {
-    const Shape& S = *g_shapes[i];
-    if (S.pat.get() == pat && S.smoother == smoother && S.phased == phased &&
-        S.r_lds == r_lds && S.single == single) {
-      auto s = g_shapes[i];
-      g_shapes.erase(g_shapes.begin() + (long)i);
-      g_shapes.push_back(s);
-      return s;
-    }
-  }
-  return nullptr;
-}
-
-void pattern_insert(const std::shared_ptr<const Pattern>& s) {
-  std::lock_guard<std::mutex> lk(g_shape_mu);
-  g_patterns.push_back(s);
-  cache_trim(g_patterns);
-}
-
-void shape_insert(const std::shared_ptr<const Shape>& s) {
-  std::lock_guard<std::mutex> lk(g_shape_mu);
-  g_shapes.push_back(s);
-  cache_trim(g_shapes);
-}
-
-// rows of a CSR pattern into a slot-major fixed-width layout: col (-1 pads) and the index of
-// each slot's value (-1 pads); width = the longest row (>= 1)
-int pack_map(int64_t rows, const int32_t* ip, const int32_t* ij, std::vector<int32_t>& col,
-             std::vector<int32_t>& map) {
-  int w = 1;
-  for (int64_t i = 0; i < rows; ++i) w = std::max(w, ip[i + 1] - ip[i]);
-  col.assign((size_t)w * rows, -1);
-  map.assign((size_t)w * rows, -1);
-  for (int64_t i = 0; i < rows; ++i)
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) {
-      col[(size_t)(k - ip[i]) * rows + i] = ij[k];
-      map[(size_t)(k - ip[i]) * rows + i] = k;
-    }
-  return w;
-}
-
-std::shared_ptr<Pattern> analyse_pattern(const mlamg_amg2v_problem& P, uint64_t key) {
-  auto Sp = std::make_shared<Pattern>();
-  Pattern& S = *Sp;
-  const int64_t n = P.n, nnz = P.A_nnz;
-  const int32_t *ip = P.A_indptr, *ij = P.A_indices;
-  S.n = n;
-  S.nc = P.n_c;
-  S.annz = nnz;
-  S.pnnz = P.P_nnz;
-  S.key = key;
-  S.aip.assign(ip, ip + n + 1);
-  S.aij.assign(ij, ij + nnz);
-  S.pip.assign(P.P_indptr, P.P_indptr + n + 1);
-  S.pij.assign(P.P_indices, P.P_indices + P.P_nnz);
-  // A's structural transpose pairing
-  std::vector<int32_t> tp(n + 1, 0), tk(nnz), tr(nnz);
-  for (int64_t k = 0; k < nnz; ++k) tp[ij[k] + 1]++;
-  for (int64_t j = 0; j < n; ++j) tp[j + 1] += tp[j];
-  std::vector<int32_t> fill(tp.begin(), tp.end() - 1);
-  for (int64_t i = 0; i < n; ++i)
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) {  // column j: rows ascending
-      tr[fill[ij[k]]] = (int32_t)i;
-      tk[fill[ij[k]]++] = k;
-    }
-  S.sym.assign(nnz, -1);
-  S.sym_ok = true;
-  std::vector<std::pair<int32_t, int32_t>> row;
-  for (int64_t i = 0; i < n; ++i) {
-    row.clear();
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) row.emplace_back(ij[k], k);
-    std::sort(row.begin(), row.end());
-    for (size_t q = 1; q < row.size(); ++q)
-      if (row[q].first == row[q - 1].first) S.dups = true;
-    if (ip[i + 1] - ip[i] != tp[i + 1] - tp[i]) {
-      S.sym_ok = false;
-      continue;
-    }
-    // column i of A (entries (r, i), r ascending) against row i's columns ascending
-    for (size_t q = 0; q < row.size(); ++q) {
-      if (tr[tp[i] + q] != row[q].first) S.sym_ok = false;
-      S.sym[row[q].second] = tk[tp[i] + q];
-    }
-  }
-  if (S.dups) S.sym_ok = false;
-  // half-bandwidth of A_H: (P^T A P)_IJ != 0 needs P_iI, A_ik, P_kJ != 0, so the lowest J of
-  // any coarse row I of fine row i is the lowest P column over i's A neighbours
-  std::vector<int32_t> pmin(n, INT32_MAX);
-  for (int64_t i = 0; i < n; ++i)
-    for (int32_t k = P.P_indptr[i]; k < P.P_indptr[i + 1]; ++k)
-      pmin[i] = std::min(pmin[i], P.P_indices[k]);
-  int band = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    int32_t am = INT32_MAX;
-    for (int32_t k = ip[i]; k < ip[i + 1]; ++k) am = std::min(am, pmin[ij[k]]);
-    if (am == INT32_MAX) continue;
-    for (int32_t k = P.P_indptr[i]; k < P.P_indptr[i + 1]; ++k)
-      band = std::max(band, P.P_indices[k] - am);
-  }
-  S.band = band;
-  return Sp;
-}
-
-// chol_lds / setup_lds: LDS bytes of the inverse-Cholesky factor (two NB x (NB+1) blocks, the
-// L21 panel and the Z rows) and of the Gauss-Jordan panel (n_c x (b+1), pivots, permutation)
-size_t chol_lds(int nb, int64_t nc) {
-  return (size_t)8 * (2 * nb * (nb + 1) + (size_t)nc * (nb + 1) + (size_t)nb * nc);
-}
-size_t band_lds(int b) {  // band_chol's rings: w x (w + 1) window, w diagonals
-  size_t w = 1;
-  while (w < (size_t)b + 2) w <<= 1;
-  return 8 * (w * (w + 1) + w);
-}
-size_t gj_lds(int b, int64_t nc) { return (size_t)nc * (b + 1) * 8 + 16 * b + (size_t)nc * 12; }
-
-// the structure analysis of one pattern (P already validated)
-std::shared_ptr<Shape> analyse_shape(const mlamg_amg2v_problem& P,
-                                     const std::shared_ptr<const Pattern>& pat, int smoother,
-                                     int phased, int r_lds, int single) {
-  auto Sp = std::make_shared<Shape>();
-  Shape& L = *Sp;
-  const int64_t n = P.n, nc = P.n_c;
-  L.pat = pat;
-  L.smoother = smoother;
-  L.phased = phased;
-  L.r_lds = r_lds;
-  L.single = single;
-  L.KA = pack_map(n, P.A_indptr, P.A_indices, L.akc, L.amap);
-  L.KP = pack_map(n, P.P_indptr, P.P_indices, L.ppc, L.pmap);
-  {  // P^T: entries of coarse column j in ascending fine row
-    std::vector<int32_t> tp(nc + 1, 0);
-    for (int64_t k = 0; k < P.P_nnz; ++k) tp[P.P_indices[k] + 1]++;
-    for (int64_t j = 0; j < nc; ++j) tp[j + 1] += tp[j];
-    std::vector<int32_t> ti(P.P_nnz), tk(P.P_nnz);
-    std::vector<int32_t> fill(tp.begin(), tp.end() - 1);
-    for (int64_t i = 0; i < n; ++i)
-      for (int32_t k = P.P_indptr[i]; k < P.P_indptr[i + 1]; ++k) {
-        const int32_t j = P.P_indices[k];
-        ti[fill[j]] = (int32_t)i;
-        tk[fill[j]++] = k;
-      }
-    L.KT = pack_map(nc, tp.data(), ti.data(), L.ptc, L.tmap);
-    // pack_map stored positions into ti/tk; map them back to P.data indices
-    for (auto& m : L.tmap)
-      if (m >= 0) m = tk[m];
-  }
-  if (L.KA > kBMaxK + 1 || L.KP > kBMaxKP || L.KT > kBMaxKT) {
-    L.code = MLAMG_EUNSUPPORTED;
-    L.err = "amg2v_batch: rows of A, P or P^T longer than the batched solver's slots";
-    return Sp;
-  }
-  int chol_nb = 16;  // the widest panel that fits (wider panels lengthen the per-thread
-                     // triangular solves more than they save in trailing passes)
-  while (chol_nb > 4 && chol_lds(chol_nb, nc) > kBLdsBytes) chol_nb >>= 1;
-  L.chol_nb = chol_nb;
-  L.chol_fits = chol_lds(chol_nb, nc) <= kBLdsBytes;
-  L.lds_chol = chol_lds(chol_nb, nc);
-  // cycle vectors in LDS: x (+ zero and sink slots), r when it fits (L^-1 r_H shares it), r_H,
-  // e_H; the sweep's staging area gets the rest
-  const size_t vec_lds = (size_t)n * 8 * (r_lds ? 2 : 1) + 16 + (phased ? 0 : (size_t)nc * 16);
-  const size_t room = kBLdsBytes > vec_lds + 64 ? kBLdsBytes - vec_lds - 64 : 0;
-  int gs_rw = 0;
-  if (smoother == 0) {
-    // level schedule of the forward sweep (gs.hip): level(i) = 1 + max level(j) over j < i
-    // coupled in either direction; rows ascending within a level
-    std::vector<int32_t> level(n, 0), req(n, 0);
-    int maxoff = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      int32_t lv = req[i];
-      int off = 0;
-      for (int32_t k = P.A_indptr[i]; k < P.A_indptr[i + 1]; ++k) {
-        const int32_t j = P.A_indices[k];
-        if (j < i) lv = std::max(lv, level[j] + 1);
-        if (j != i) ++off;
-      }
-      level[i] = lv;
-      maxoff = std::max(maxoff, off);
-      for (int32_t k = P.A_indptr[i]; k < P.A_indptr[i + 1]; ++k) {
-        const int32_t j = P.A_indices[k];
-        if (j > i) req[j] = std::max(req[j], lv + 1);
-      }
-      L.nlev = std::max(L.nlev, lv + 1);
-    }
-    if (maxoff > kBMaxK) {
-      L.code = MLAMG_EUNSUPPORTED;
-      L.err = "amg2v_batch: a row of A has more than 32 off-diagonal entries";
-      return Sp;
-    }
-    L.lev.assign(L.nlev + 1, 0);
-    for (int64_t i = 0; i < n; ++i) L.lev[level[i] + 1]++;
-    for (int l = 0; l < L.nlev; ++l) L.lev[l + 1] += L.lev[l];
-    int wmax = 0;
-    for (int l = 0; l < L.nlev; ++l) wmax = std::max(wmax, L.lev[l + 1] - L.lev[l]);
-    // one-wave sweep: rows of 4 slots and levels of <= 128 rows, or 8 slots and <= 64 rows,
-    // and a staging area that holds the widest level (+ the dummy position)
-    const int km = maxoff <= 4 ? 4 : maxoff <= 8 ? 8 : 0;
-    if (km == 4 && wmax <= 128) gs_rw = wmax <= 64 ? 1 : 2;
-    if (km == 8 && wmax <= 64) gs_rw = 1;
-    if (gs_rw && (int)std::min<size_t>(4096, room / (12 * km + 24)) - 1 < wmax) gs_rw = 0;
-    // two staging buffers when each still holds >= 3 of the widest levels
-    static const bool no_db = std::getenv("MLAMG_BATCH_NO_DB") != nullptr;  // A/B knob
-    if (gs_rw && !no_db &&
-        (int)std::min<size_t>(4096, room / (2 * (12 * km + 24) + 16)) - 1 >= 3 * wmax)
-      L.gs_db = 1;
-    L.K = gs_rw ? km : std::max(maxoff, 1);
-    const int64_t K = L.K;
-    L.pkr0.resize(n);
-    L.pkc.assign((size_t)n * K, gs_rw ? (int32_t)n : -1);
-    L.gmap.assign((size_t)n * K, -1);
-    L.dmap.assign(n, -1);
-    std::vector<int32_t> fill(L.lev.begin(), L.lev.end() - 1);
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t p = fill[level[i]]++;
-      L.pkr0[p] = (int32_t)i;
-      int s2 = 0;
-      for (int32_t k = P.A_indptr[i]; k < P.A_indptr[i + 1]; ++k) {
-        if (P.A_indices[k] == i) {
-          L.dmap[p] = k;  // the last stored diagonal entry, as the sweep takes it
-        } else {
-          // slot-major for the workgroup sweep, position-major for the one-wave sweep
-          const size_t at = gs_rw ? (size_t)p * K + s2 : (size_t)s2 * n + p;
-          L.pkc[at] = P.A_indices[k];
-          L.gmap[at] = k;
-          ++s2;
-        }
+  const int32_t* done_dev = reinterpret_cast<const int32_t*>(L.arena + plan.done_off);
+  constexpr int kPhaseBatch = 4;
+  int a = 0;
+  for (int batch = 0; a < total_a; ++batch) {
+    const int na = tol >= 0.0 ? std::min(kPhaseBatch, total_a - a) : total_a - a;
+    for (int q = 0; q < na; ++q, ++a) {
+      launch_cycle_kernel<true>(L);
+      if (a < max_iter) {
+        hipLaunchKernelGGL(k_amg2v_coarse<1>, dim3(coarse_blocks), dim3(256), 0, s, L.dd(),
+                           L.arena, cb, count);
+        if (plan.two_pass)  // the one-workgroup inverse Cholesky factors' L^-T pass
+          hipLaunchKernelGGL(k_amg2v_coarse<2>, dim3(coarse_blocks), dim3(256), 0, s, L.dd(),
+                             L.arena, cb, count);
       }
     }
-  }
-  // panel width: the widest power of two <= 16 whose n_c x (b+1) panel (+ pivots and the
-  // final column permutation) fits
-  int pb = kBMaxPanel;
-  while (pb > 4 && gj_lds(pb, nc) > kBLdsBytes) pb >>= 1;
-  if (gj_lds(pb, nc) > kBLdsBytes) {
-    L.code = MLAMG_EINVAL;
-    L.err = "coarse too large";
-    return Sp;
-  }
-  L.panel = pb;
-  // GS staging chunks: runs of consecutive levels with <= cap rows, cap from the LDS left
-  // after the cycle vectors, one position kept for the one-wave sweep's dummy (a level wider
-  // than cap is swept by the workgroup straight from the arena)
-  if (smoother == 0) {
-    const size_t per_pos = (12 * (size_t)L.K + 24) * (L.gs_db ? 2 : 1);
-    const size_t slack = L.gs_db ? 32 : 0;
-    L.cap = (int)std::min<size_t>(4096, (room > slack ? room - slack : 0) / per_pos) - 1;
-    L.clev.push_back(0);
-    int l = 0;
-    while (l < L.nlev) {
-      const int start = l;
-      int cnt = 0;
-      while (l < L.nlev && (l == start || cnt + (L.lev[l + 1] - L.lev[l]) <= L.cap)) {
-        cnt += L.lev[l + 1] - L.lev[l];
-        ++l;
-      }
-      L.clev.push_back(l);
+    MLAMG_HIP(hipGetLastError());
+    if (tol < 0.0 || a >= total_a) break;
+    MLAMG_HIP(hipMemcpyAsync(pf.host + (batch & 1), done_dev, sizeof(int32_t),
+                             hipMemcpyDeviceToHost, s));
+    MLAMG_HIP(hipEventRecord(pf.ev[batch & 1], s));
+    if (batch > 0) {
+      MLAMG_HIP(hipEventSynchronize(pf.ev[(batch - 1) & 1]));
+      if (pf.host[(batch - 1) & 1] >= count) break;
     }
   }
-  static const bool no_rp = std::getenv("MLAMG_BATCH_NO_RP") != nullptr;  // A/B knob
-  if (phased && single && gs_rw && !L.gs_db && !no_rp && L.cap + 1 <= kBT - 64 &&
-      L.cap * L.K <= 2 * (kBT - 64))
-    L.gs_rp = 1;
-  L.lds_base = gj_lds(pb, nc);
-  L.lds_cycles = vec_lds + 16 + (size_t)(L.cap + 1) * (12 * L.K + 24) * (L.gs_db ? 2 : 1) + 40;
-  L.gs_rw = gs_rw;
-  return Sp;
+  return MLAMG_OK;
+}
+
+// MLAMG_BATCH_TIMING: the kernels' phase stamps of every problem (host_out: the output part)
+void print_problem_timing(const BatchPlan& plan, const mlamg_amg2v_problem* probs,
+                          const char* host_out) {
+  for (size_t q = 0; q < plan.desc.size(); ++q) {
+    const BDesc& D = plan.desc[q];
+    const int32_t* st = reinterpret_cast<const int32_t*>(host_out + (D.stat_out - plan.out_begin));
+    const int64_t* ts = reinterpret_cast<const int64_t*>(st + 4);
+    std::fprintf(stderr,
+                 "[amg2v_batch] problem %d n=%lld n_c=%lld iters=%d: galerkin %.3f ms, inverse "
+                 "(%s) %.3f ms (panels %.3f, updates %.3f), smoothing (%s) %.3f ms, rest of "
+                 "cycles %.3f ms (coarse solve %.3f ms)\n",
+                 (int)q, (long long)probs[q].n, (long long)probs[q].n_c, st[0], ts[0] * 1e-5,
+                 st[2] == 2 ? "band cholesky" : st[2] == 1 ? "cholesky" : "gauss-jordan",
+                 (ts[1] + ts[4] + ts[5]) * 1e-5, ts[4] * 1e-5, ts[5] * 1e-5,
+                 D.gs_rw ? "one wave" : "workgroup", ts[2] * 1e-5, (ts[3] + ts[6]) * 1e-5,
+                 ts[6] * 1e-5);
+  }
 }
 
 }  // namespace
@@ -2299,495 +1893,46 @@ int mlamg_amg2v_batch(mlamg_amg2v_problem* probs, int count, int smoother, int n
   MLAMG_REQUIRE(nu_pre >= 0 && nu_post >= 0 && max_iter >= 0, "negative count");
   if (count == 0) return MLAMG_OK;
   hipStream_t s = S(stream);
-  // ---- host: validation, patterns (flag-independent analysis), per-problem value checks, the
-  // batch's strategy, shapes (flag-dependent analysis); patterns and shapes cached across calls
-  static const bool timing = std::getenv("MLAMG_BATCH_TIMING") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  std::vector<BDesc> desc(count);
-  const bool no_cache = std::getenv("MLAMG_BATCH_NO_SHAPE_CACHE") != nullptr;  // A/B knob
-  const bool no_band = std::getenv("MLAMG_BATCH_NO_BAND") != nullptr;         // A/B knob
-  // 1. validation and the pattern key of every problem (host threads)
-  std::vector<int> vcode(count, MLAMG_OK);
-  std::vector<const char*> verr(count, nullptr);
-  std::vector<uint64_t> key(count, 0);
-  parallel_for(count, [&](int q) {
-    const mlamg_amg2v_problem& P = probs[q];
-    auto fail = [&](const char* m) {
-      vcode[q] = MLAMG_EINVAL;
-      verr[q] = m;
-    };
-    const int64_t n = P.n, nc = P.n_c;
-    if (!(n >= 1 && n <= kBMaxN)) return fail("problem rows out of range for the batched solver");
-    if (!(nc >= 1 && nc <= kBMaxNc && nc <= n)) return fail("coarse size out of range");
-    if (!(valid_csr(n, n, P.A_nnz, P.A_indptr, P.A_indices) && P.A_data))
-      return fail("A is not a valid n x n CSR");
-    if (!(valid_csr(n, nc, P.P_nnz, P.P_indptr, P.P_indices) && P.P_data))
-      return fail("P is not a valid n x n_c CSR");
-    if (!(P.b && P.x0 && P.x_out && (max_iter == 0 || P.err_out))) return fail("NULL vector");
-    key[q] = pattern_key(P);
-  });
-  for (int q = 0; q < count; ++q)
-    if (vcode[q] != MLAMG_OK) {
-      set_error(std::string(verr[q]) + " (problem " + std::to_string(q) + ")");
-      return vcode[q];
-    }
-  // 2. group by key (a representative per distinct key), members compared in full (a key
-  // collision leaves the member its own pattern); patterns from the cache or analysed
-  std::vector<int> rep(count);
-  {
-    std::vector<std::pair<uint64_t, int>> order(count);
-    for (int q = 0; q < count; ++q) order[q] = {key[q], q};
-    std::sort(order.begin(), order.end());
-    for (int t = 0; t < count; ++t)
-      rep[order[t].second] = t > 0 && order[t].first == order[t - 1].first
-                                 ? rep[order[t - 1].second]
-                                 : order[t].second;
+  using clock = std::chrono::steady_clock;
+  const auto t_begin = clock::now();
+  // host: validation, analysis (cached across calls), strategy, arena layout (batch_plan.cpp)
+  BatchPlan plan;
+  if (plan_batch(probs, count, smoother, nu_pre, nu_post, jacobi_weight, norm_mode, tol, max_iter,
+                 &plan) != MLAMG_OK) {
+    set_error(plan.err);
+    return plan.code;
   }
-  parallel_for(count, [&](int q) {
-    if (rep[q] != q && !same_pattern(probs[q], probs[rep[q]])) rep[q] = q;
-  });
-  std::vector<std::shared_ptr<const Pattern>> pat(count);
-  std::vector<int> todo;
-  for (int q = 0; q < count; ++q)
-    if (rep[q] == q) {
-      if (!no_cache) pat[q] = pattern_lookup(key[q], probs[q]);
-      if (!pat[q]) todo.push_back(q);
-    }
-  parallel_for((int)todo.size(), [&](int t) {
-    const int q = todo[t];
-    auto S = analyse_pattern(probs[q], key[q]);
-    if (!no_cache) pattern_insert(S);
-    pat[q] = S;
-  });
-  for (int q = 0; q < count; ++q) pat[q] = pat[rep[q]];
-  // 3. per problem: A == A^T exactly (values included) -> an SPD coarse operator, factored as a
-  // band when its structure is narrow, else as a dense inverse Cholesky factor
-  std::vector<char> sym(count, 0), band(count, 0);
-  parallel_for(count, [&](int q) {
-    const Pattern& S = *pat[q];
-    const mlamg_amg2v_problem& P = probs[q];
-    bool s = false;
-    if (S.sym_ok) {
-      s = true;
-      for (int64_t k = 0; k < S.annz && s; ++k) s = P.A_data[k] == P.A_data[S.sym[k]];
-    } else if (S.dups) {
-      s = csr_symmetric(P.n, P.A_indptr, P.A_indices, P.A_data);
-    }
-    sym[q] = s ? 1 : 0;
-    band[q] = s && !no_band && S.band <= kBandMax && S.nc <= kBandMaxNc &&
-              band_lds(S.band) <= kBLdsBytes ? 1 : 0;
-  });
-  // 4. strategy. A single problem with a large dense coarse operator: the coarse inverse from
-  // the device-wide factorisation (dense.hip) and phased cycles, the coarse solve on every CU.
-  // Batches holding such problems run phased too (each problem's cycles on its workgroup, the
-  // dense coarse solves spread over the CUs; banded problems solve on their own workgroup)
-  static const int ext_min = [] {
-    const char* e = std::getenv("MLAMG_BATCH_EXT_MIN");
-    return e ? std::atoi(e) : kExtCoarseMin;
-  }();
-  const bool no_ext = std::getenv("MLAMG_BATCH_NO_EXT") != nullptr;
-  bool big_dense = false;
-  for (int q = 0; q < count; ++q) big_dense = big_dense || (!band[q] && probs[q].n_c > ext_min);
-  const bool ext_ok = count == 1 && big_dense && !no_ext;
-  const bool phased_batch = count > 1 && big_dense && !no_ext &&
-                            !std::getenv("MLAMG_BATCH_NO_PHASED_BATCH");
-  const bool phased = (ext_ok || phased_batch) && !std::getenv("MLAMG_BATCH_NO_PHASED");
-  // residual in LDS when every problem leaves room for it (phased: r_H, e_H live in the arena)
-  bool r_lds = true;
-  for (int q = 0; q < count; ++q) {
-    const size_t need = (size_t)probs[q].n * 16 + 16 + (phased ? 0 : (size_t)probs[q].n_c * 16) +
-                        16 * 1024;
-    if (need > kBLdsBytes) r_lds = false;
-  }
-  const int single = count == 1 ? 1 : 0;
-  // 5. shapes for these flags (cached per pattern)
-  std::vector<std::shared_ptr<const Shape>> shape(count);
-  todo.clear();
-  for (int q = 0; q < count; ++q)
-    if (rep[q] == q) {
-      if (!no_cache) shape[q] = shape_lookup(pat[q].get(), smoother, phased, r_lds, single);
-      if (!shape[q]) todo.push_back(q);
-    }
-  parallel_for((int)todo.size(), [&](int t) {
-    const int q = todo[t];
-    auto S = analyse_shape(probs[q], pat[q], smoother, phased, r_lds, single);
-    if (S->code == MLAMG_OK && !no_cache) shape_insert(S);
-    shape[q] = S;
-  });
-  for (int q = 0; q < count; ++q) shape[q] = shape[rep[q]];
-  for (int q = 0; q < count; ++q)
-    if (shape[q]->code != MLAMG_OK) {
-      set_error(shape[q]->err + " (problem " + std::to_string(q) + ")");
-      return shape[q]->code;
-    }
-  // the dense inverse Cholesky factor where no band is taken and it fits one workgroup's LDS
-  std::vector<char> spd(count, 0);
-  for (int q = 0; q < count; ++q) spd[q] = sym[q] && !band[q] && shape[q]->chol_fits ? 1 : 0;
-  const auto t_analysed = std::chrono::steady_clock::now();
-  // ---- layout: each distinct shape's structure once, then every problem's values
-  Layout lay;
-  const int64_t desc_off = lay.take(sizeof(BDesc) * count);
-  size_t lds_setup = 0, lds_cycles = 0, lds_band = 0;
-  bool any_band = false;
-  for (int q = 0; q < count; ++q) any_band = any_band || band[q];
-  struct ShapeOffs {
-    int64_t akc, amap, ppc, pmap, ptc, tmap, lev, clev, pkc, gmap, dmap, pkr0;
-  };
-  std::vector<const Shape*> uniq;
-  std::vector<ShapeOffs> uoff;
-  std::vector<int> uidx(count, -1);
-  for (int q = 0; q < count; ++q) {
-    if (rep[q] != q) {
-      uidx[q] = uidx[rep[q]];
-      continue;
-    }
-    const Shape& S = *shape[q];
-    ShapeOffs o;
-    o.akc = lay.take(4 * S.akc.size());
-    o.amap = lay.take(4 * S.amap.size());
-    o.ppc = lay.take(4 * S.ppc.size());
-    o.pmap = lay.take(4 * S.pmap.size());
-    o.ptc = lay.take(4 * S.ptc.size());
-    o.tmap = lay.take(4 * S.tmap.size());
-    o.lev = lay.take(4 * S.lev.size());
-    o.clev = lay.take(4 * S.clev.size());
-    o.pkc = lay.take(4 * S.pkc.size());
-    o.gmap = lay.take(4 * S.gmap.size());
-    o.dmap = lay.take(4 * S.dmap.size());
-    o.pkr0 = lay.take(4 * S.pkr0.size());
-    uidx[q] = (int)uniq.size();
-    uniq.push_back(&S);
-    uoff.push_back(o);
-  }
-  for (int q = 0; q < count; ++q) {
-    const Shape& L = *shape[q];
-    const ShapeOffs& o = uoff[uidx[q]];
-    lds_setup = std::max(lds_setup, std::max(L.lds_base, spd[q] ? L.lds_chol : size_t(0)));
-    if (band[q]) lds_band = std::max(lds_band, band_lds(pat[q]->band));
-    lds_cycles = std::max(lds_cycles, L.lds_cycles);
-    const mlamg_amg2v_problem& P = probs[q];
-    const int64_t n = P.n;
-    BDesc& D = desc[q];
-    std::memset(&D, 0, sizeof(D));
-    D.n = (int32_t)n;
-    D.nc = (int32_t)P.n_c;
-    D.smoother = smoother;
-    D.nu_pre = nu_pre;
-    D.nu_post = nu_post;
-    D.norm_mode = norm_mode;
-    D.max_iter = max_iter;
-    D.K = L.K;
-    D.KA = L.KA;
-    D.KP = L.KP;
-    D.KT = L.KT;
-    D.nlev = L.nlev;
-    D.panel = L.panel;
-    D.n_chunks = L.clev.empty() ? 0 : (int32_t)L.clev.size() - 1;
-    D.cap = L.cap;
-    D.timing = timing ? 1 : 0;
-    D.spd = spd[q];
-    D.band_ld = band[q] ? pat[q]->band + 1 : 0;
-    D.chol_nb = L.chol_nb;
-    D.gs_rw = L.gs_rw;
-    D.gs_db = L.gs_db;
-    D.gs_rp = L.gs_rp;
-    D.phased = phased ? 1 : 0;
-    D.tol = tol;
-    D.omega = jacobi_weight;
-    D.ak_col = o.akc;
-    D.a_map = o.amap;
-    D.pp_col = o.ppc;
-    D.p_map = o.pmap;
-    D.pt_row = o.ptc;
-    D.t_map = o.tmap;
-    D.lev_ptr = o.lev;
-    D.chunk_lev = o.clev;
-    D.pk_col = o.pkc;
-    D.g_map = o.gmap;
-    D.d_map = o.dmap;
-    D.pk_row0 = o.pkr0;
-    D.a_raw = lay.take(8 * (size_t)P.A_nnz);
-    D.p_raw = lay.take(8 * (size_t)P.P_nnz);
-    D.b = lay.take(8 * n);
-    D.x0 = lay.take(8 * n);
-  }
-  // phased: each problem's first coarse-solve block (k_amg2v_coarse), a row per wave
-  const int64_t cblk_off = phased ? lay.take(4 * (size_t)(count + 1)) : 0;
-  std::vector<int32_t> cblk(count + 1, 0);
-  for (int q = 0; q < count; ++q) cblk[q + 1] = cblk[q] + (int32_t)((desc[q].nc + 3) / 4);
-  MLAMG_REQUIRE(lds_setup <= kBLdsBytes + 1024 && lds_cycles <= kBLdsBytes + 1024,
-                "LDS budget exceeded");
-  const size_t in_bytes = lay.off;
-  for (int q = 0; q < count; ++q) {
-    BDesc& D = desc[q];
-    const Shape& L = *shape[q];
-    // the packed values, gathered on the device (gather_values)
-    D.ak_val = lay.take(8 * L.akc.size());
-    D.pp_val = lay.take(8 * L.ppc.size());
-    D.pt_val = lay.take(8 * L.ptc.size());
-    D.pk_val = lay.take(8 * L.pkc.size());
-    D.pk_diag = lay.take(8 * L.pkr0.size());
-    D.pk_row = lay.take(4 * L.pkr0.size());
-    D.b_lvl = lay.take(8 * L.pkr0.size());
-    D.AH = lay.take((size_t)8 * D.nc * D.nc);
-    D.AI = lay.take((size_t)8 * D.nc * D.nc);
-    D.rg = lay.take(8 * (size_t)D.n);
-    D.dinv = lay.take(8 * (size_t)D.n);
-    if (D.band_ld > 0) {  // the band solve's lane layouts (band_chol), padded
-      D.lc = lay.take((size_t)8 * 64 * (D.nc + 2 * kBandPad));
-      D.lr = lay.take((size_t)8 * 64 * (D.nc + 2 * kBandPad));
-      D.rinv = lay.take((size_t)8 * (D.nc + 2 * kBandPad));
-    }
-    if (phased) {
-      D.rcg = lay.take(8 * (size_t)D.nc);
-      D.eg = lay.take(8 * (size_t)D.nc);
-      D.yg = lay.take(8 * (size_t)D.nc);
-    }
-  }
-  const int64_t done_off = phased ? lay.take(sizeof(int32_t)) : 0;
-  for (int q = 0; q < count; ++q) desc[q].done_ctr = done_off;
-  const size_t out_begin = lay.off;
-  for (int q = 0; q < count; ++q) {
-    BDesc& D = desc[q];
-    D.x_out = lay.take(8 * (size_t)D.n);
-    D.err_out = lay.take(8 * (size_t)std::max(max_iter, 1));
-    D.stat_out = lay.take(16 + 8 * 8);
-  }
-  const size_t total = lay.off;
-  // a single problem with a large SPD coarse operator takes the device-wide coarse factorisation
-  const bool ext_coarse = ext_ok && spd[0];
-  if (ext_coarse) desc[0].setup_mode = 1;
-  // a phased batch factors its large SPD operators device-wide too, all in one launch sequence.
-  // The factor is chosen by the problem's own n_c, as a single call chooses it (the batched and
-  // the single device-wide factors run the same code per operator): a problem's results do not
-  // depend on the batch it is launched with
-  const bool batch_ext = phased && count > 1 && !std::getenv("MLAMG_BATCH_NO_BATCH_EXT");
-  if (batch_ext)
-    for (int q = 0; q < count; ++q)
-      if (spd[q] && desc[q].nc > ext_min) desc[q].setup_mode = 2;
-  // ---- pack the inputs into pinned host memory, one copy in
-  HostPinned& H = g_batch_host;
-  const size_t host_need = std::max(in_bytes, total - out_begin);
-  if (H.cap < host_need) {
-    if (H.p) (void)hipHostFree(H.p);
-    H.p = nullptr;
-    H.cap = 0;
-    const size_t grow = host_need + host_need / 2;  // geometric: batches of similar size reuse it
-    MLAMG_HIP(hipHostMalloc(&H.p, grow, hipHostMallocDefault));
-    H.cap = grow;
-  }
-  char* hb = static_cast<char*>(H.p);
-  const auto t_pinned = std::chrono::steady_clock::now();
-  std::memcpy(hb + desc_off, desc.data(), sizeof(BDesc) * count);
-  if (phased) std::memcpy(hb + cblk_off, cblk.data(), 4 * (size_t)(count + 1));
-  auto put = [&](int64_t off, const void* src, size_t bytes) {
-    if (bytes) std::memcpy(hb + off, src, bytes);
-  };
-  const int nu = (int)uniq.size();
-  parallel_for(nu + count, [&](int t) {
-    if (t < nu) {  // a shape's structure
-      const Shape& S = *uniq[t];
-      const ShapeOffs& o = uoff[t];
-      put(o.akc, S.akc.data(), 4 * S.akc.size());
-      put(o.amap, S.amap.data(), 4 * S.amap.size());
-      put(o.ppc, S.ppc.data(), 4 * S.ppc.size());
-      put(o.pmap, S.pmap.data(), 4 * S.pmap.size());
-      put(o.ptc, S.ptc.data(), 4 * S.ptc.size());
-      put(o.tmap, S.tmap.data(), 4 * S.tmap.size());
-      put(o.lev, S.lev.data(), 4 * S.lev.size());
-      put(o.clev, S.clev.data(), 4 * S.clev.size());
-      put(o.pkc, S.pkc.data(), 4 * S.pkc.size());
-      put(o.gmap, S.gmap.data(), 4 * S.gmap.size());
-      put(o.dmap, S.dmap.data(), 4 * S.dmap.size());
-      put(o.pkr0, S.pkr0.data(), 4 * S.pkr0.size());
-      return;
-    }
-    const int q = t - nu;  // a problem's values
-    const mlamg_amg2v_problem& P = probs[q];
-    const BDesc& D = desc[q];
-    put(D.a_raw, P.A_data, 8 * (size_t)P.A_nnz);
-    put(D.p_raw, P.P_data, 8 * (size_t)P.P_nnz);
-    put(D.b, P.b, 8 * (size_t)P.n);
-    put(D.x0, P.x0, 8 * (size_t)P.n);
-  });
-  const auto t_filled = std::chrono::steady_clock::now();
-  char* arena = static_cast<char*>(scratch(total, 11));
+  // the inputs packed into pinned host memory, one copy in
+  char* hb = nullptr;
+  MLAMG_TRY(pinned_buffer(std::max(plan.in_bytes, plan.total - plan.out_begin), &hb));
+  const auto t_pinned = clock::now();
+  fill_inputs(plan, probs, hb);
+  const auto t_filled = clock::now();
+  char* arena = static_cast<char*>(scratch(plan.total, 11));
   MLAMG_REQUIRE(arena, "device arena allocation failed");
-  const auto t_packed = std::chrono::steady_clock::now();
-  MLAMG_HIP(hipMemcpyAsync(arena, hb, in_bytes, hipMemcpyHostToDevice, s));
-  const BDesc* dd = reinterpret_cast<const BDesc*>(arena + desc_off);
-  hipLaunchKernelGGL(k_amg2v_setup, dim3((unsigned)count), dim3(kBT), lds_setup, s, dd, arena, 0);
-  if (any_band) {  // band factors, then Gauss-Jordan for any that met a non-positive pivot
-    hipLaunchKernelGGL(k_amg2v_band, dim3((unsigned)count), dim3(kBT), lds_band, s, dd, arena);
-    hipLaunchKernelGGL(k_amg2v_setup, dim3((unsigned)count), dim3(kBT), lds_setup, s, dd, arena, 1);
-  }
-  if (ext_coarse) {
-    const int nc = desc[0].nc;
-    const int R = std::max(1, std::min(64, (int)((size_t)128 * 1024 / (8 * (size_t)nc))));
-    hipLaunchKernelGGL(k_galerkin_rows, dim3((unsigned)((nc + R - 1) / R)), dim3(256),
-                       (size_t)R * nc * 8, s, dd, arena, R);
-    // a single call with a large SPD coarse operator: the device-wide inverse Cholesky factor
-    // (all CUs) instead of one workgroup's; Gauss-Jordan in the setup kernel when not SPD
-    const BDesc& D = desc[0];
-    bool spd = false;
-    MLAMG_TRY(dense_chol_inverse(reinterpret_cast<double*>(arena + D.AH), D.nc,
-                                 reinterpret_cast<double*>(arena + D.AI), &spd, s));
-    if (!spd) {
-      BDesc& Dh = *reinterpret_cast<BDesc*>(hb + desc_off);
-      Dh.setup_mode = 0;
-      Dh.spd = 0;
-      MLAMG_HIP(hipMemcpyAsync(arena + desc_off, hb + desc_off, sizeof(BDesc),
-                               hipMemcpyHostToDevice, s));
-      MLAMG_HIP(hipStreamSynchronize(s));
-      hipLaunchKernelGGL(k_amg2v_setup, dim3(1), dim3(kBT), lds_setup, s, dd, arena, 0);
-    }
-  }
-  if (batch_ext) {
-    std::vector<DenseJob> jobs;
-    std::vector<int> who;
-    for (int q = 0; q < count; ++q)
-      if (desc[q].setup_mode == 2) {
-        DenseJob J{};
-        J.M = reinterpret_cast<double*>(arena + desc[q].AH);
-        J.inv = reinterpret_cast<double*>(arena + desc[q].AI);
-        J.n = desc[q].nc;
-        jobs.push_back(J);
-        who.push_back(q);
-      }
-    std::unique_ptr<bool[]> ok(new bool[std::max<size_t>(jobs.size(), 1)]);
-    MLAMG_TRY(dense_chol_inverse_batch(jobs.data(), (int)jobs.size(), ok.get(), s));
-    bool any_failed = false;
-    for (size_t j = 0; j < jobs.size(); ++j) any_failed = any_failed || !ok[j];
-    if (any_failed) {  // Gauss-Jordan in the setup kernel for those, the others untouched
-      BDesc* Dh = reinterpret_cast<BDesc*>(hb + desc_off);
-      for (int q = 0; q < count; ++q) Dh[q].setup_mode = 3;
-      for (size_t j = 0; j < jobs.size(); ++j)
-        if (!ok[j]) {
-          Dh[who[j]].setup_mode = 0;
-          Dh[who[j]].spd = 0;
-        }
-      MLAMG_HIP(hipMemcpyAsync(arena + desc_off, hb + desc_off, sizeof(BDesc) * count,
-                               hipMemcpyHostToDevice, s));
-      MLAMG_HIP(hipStreamSynchronize(s));
-      hipLaunchKernelGGL(k_amg2v_setup, dim3((unsigned)count), dim3(kBT), lds_setup, s, dd,
-                         arena, 0);
-    }
-  }
-  if (phased) {
-    // cycle k = launches A_k (second half of cycle k - 1, first half of cycle k) and B_k (the
-    // coarse solve); A_max_iter ends it. Every launch after the one that met the tolerance
-    // returns at once; with a tolerance the host queues batches of cycles and reads the done
-    // flag of the batch before the one it just queued, so the GPU never waits for the host.
-    const bool rp = count == 1 && desc[0].gs_rp != 0;
-    const dim3 ga((unsigned)count);
-    auto launch_a = [&]() {
-      if (r_lds && rp)
-        hipLaunchKernelGGL((k_amg2v_cycles<true, true, true>), ga, dim3(kBT), lds_cycles, s, dd,
-                           arena);
-      else if (r_lds)
-        hipLaunchKernelGGL((k_amg2v_cycles<true, true, false>), ga, dim3(kBT), lds_cycles, s, dd,
-                           arena);
-      else if (rp)
-        hipLaunchKernelGGL((k_amg2v_cycles<false, true, true>), ga, dim3(kBT), lds_cycles, s,
-                           dd, arena);
-      else
-        hipLaunchKernelGGL((k_amg2v_cycles<false, true, false>), ga, dim3(kBT), lds_cycles, s,
-                           dd, arena);
-    };
-    const unsigned coarse_blocks = (unsigned)cblk[count];
-    const int32_t* cb = reinterpret_cast<const int32_t*>(arena + cblk_off);
-    // mode-1 problems (one-workgroup inverse Cholesky factor) need the second, L^-T, pass
-    bool two_pass = false;
-    for (int q = 0; q < count; ++q)
-      two_pass = two_pass || (spd[q] && desc[q].setup_mode == 0);
-    MLAMG_HIP(hipMemsetAsync(arena + done_off, 0, sizeof(int32_t), s));
-    const int total_a = max_iter + 1;
-    // per host thread: two pinned done-count slots and their events (freed at thread exit)
-    struct PhaseFlags {
-      int32_t* host = nullptr;
-      hipEvent_t ev[2] = {nullptr, nullptr};
-      ~PhaseFlags() {
-        for (auto e : ev)
-          if (e) (void)hipEventDestroy(e);
-        if (host) (void)hipHostFree(host);
-      }
-    };
-    static thread_local PhaseFlags pf;
-    if (!pf.host) {
-      MLAMG_HIP(hipHostMalloc(&pf.host, 2 * sizeof(int32_t), hipHostMallocDefault));
-      for (auto& e : pf.ev) MLAMG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    int32_t* flag_host = pf.host;
-    hipEvent_t* flag_ev = pf.ev;
-    const int32_t* done_dev = reinterpret_cast<const int32_t*>(arena + done_off);
-    constexpr int kPhaseBatch = 4;
-    int a = 0;
-    for (int batch = 0; a < total_a; ++batch) {
-      const int na = tol >= 0.0 ? std::min(kPhaseBatch, total_a - a) : total_a - a;
-      for (int q = 0; q < na; ++q, ++a) {
-        launch_a();
-        if (a < max_iter) {
-          hipLaunchKernelGGL(k_amg2v_coarse<1>, dim3(coarse_blocks), dim3(256), 0, s, dd, arena,
-                             cb, count);
-          if (two_pass)
-            hipLaunchKernelGGL(k_amg2v_coarse<2>, dim3(coarse_blocks), dim3(256), 0, s, dd,
-                               arena, cb, count);
-        }
-      }
-      MLAMG_HIP(hipGetLastError());
-      if (tol < 0.0 || a >= total_a) break;
-      MLAMG_HIP(hipMemcpyAsync(flag_host + (batch & 1), done_dev, sizeof(int32_t),
-                               hipMemcpyDeviceToHost, s));
-      MLAMG_HIP(hipEventRecord(flag_ev[batch & 1], s));
-      if (batch > 0) {
-        MLAMG_HIP(hipEventSynchronize(flag_ev[(batch - 1) & 1]));
-        if (flag_host[(batch - 1) & 1] >= count) break;
-      }
-    }
-  } else if (r_lds) {
-    hipLaunchKernelGGL((k_amg2v_cycles<true, false, false>), dim3((unsigned)count), dim3(kBT),
-                       lds_cycles, s, dd, arena);
-  } else {
-    hipLaunchKernelGGL((k_amg2v_cycles<false, false, false>), dim3((unsigned)count), dim3(kBT),
-                       lds_cycles, s, dd, arena);
-  }
+  const auto t_packed = clock::now();
+  MLAMG_HIP(hipMemcpyAsync(arena, hb, plan.in_bytes, hipMemcpyHostToDevice, s));
+  const Launch L{plan, hb, arena, s};
+  MLAMG_TRY(launch_setup(L));
+  MLAMG_TRY(launch_cycles(L, tol, max_iter));
   MLAMG_HIP(hipGetLastError());
   // the host staging buffer is reused for the outputs: the copy-in above completed before the
   // kernel (same stream), and the copy-out below is ordered after it
-  MLAMG_HIP(hipMemcpyAsync(hb, arena + out_begin, total - out_begin, hipMemcpyDeviceToHost, s));
+  MLAMG_HIP(hipMemcpyAsync(hb, arena + plan.out_begin, plan.total - plan.out_begin,
+                           hipMemcpyDeviceToHost, s));
   MLAMG_HIP(hipStreamSynchronize(s));
-  if (timing) {
-    const auto t_done = std::chrono::steady_clock::now();
+  if (plan.timing) {
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::fprintf(stderr,
                  "[amg2v_batch] %d problems: host %.3f ms (analysis %.3f, layout + pinned buffer "
                  "%.3f, fill %.3f, device arena %.3f), copy in + kernels + copy out %.3f ms "
                  "(%.2f MB in)\n",
-                 count, ms(t_begin, t_packed), ms(t_begin, t_analysed), ms(t_analysed, t_pinned),
-                 ms(t_pinned, t_filled), ms(t_filled, t_packed), ms(t_packed, t_done),
-                 in_bytes * 1e-6);
+                 count, ms(t_begin, t_packed), ms(t_begin, plan.t_analysed),
+                 ms(plan.t_analysed, t_pinned), ms(t_pinned, t_filled), ms(t_filled, t_packed),
+                 ms(t_packed, clock::now()), plan.in_bytes * 1e-6);
+    print_problem_timing(plan, probs, hb);
   }
-  for (int q = 0; q < count; ++q) {
-    mlamg_amg2v_problem& P = probs[q];
-    const BDesc& D = desc[q];
-    const int32_t* st = reinterpret_cast<const int32_t*>(hb + (D.stat_out - out_begin));
-    P.iters_out = st[0];
-    P.status_out = st[1];
-    if (timing) {
-      const int64_t* ts = reinterpret_cast<const int64_t*>(st + 4);
-      std::fprintf(stderr,
-                   "[amg2v_batch] problem %d n=%lld n_c=%lld iters=%d: galerkin %.3f ms, inverse "
-                   "(%s) %.3f ms (panels %.3f, updates %.3f), smoothing (%s) %.3f ms, rest of "
-                   "cycles %.3f ms (coarse solve %.3f ms)\n",
-                   q, (long long)P.n, (long long)P.n_c, st[0], ts[0] * 1e-5,
-                   st[2] == 2 ? "band cholesky" : st[2] == 1 ? "cholesky" : "gauss-jordan",
-                   (ts[1] + ts[4] + ts[5]) * 1e-5, ts[4] * 1e-5, ts[5] * 1e-5,
-                   D.gs_rw ? "one wave" : "workgroup", ts[2] * 1e-5, (ts[3] + ts[6]) * 1e-5,
-                   ts[6] * 1e-5);
-    }
-    std::memcpy(P.x_out, hb + (D.x_out - out_begin), 8 * (size_t)P.n);
-    if (max_iter > 0) std::memcpy(P.err_out, hb + (D.err_out - out_begin), 8 * (size_t)st[0]);
-  }
+  read_outputs(plan, probs, hb, max_iter);
   return MLAMG_OK;
 }
 

@@ -1,7 +1,9 @@
 #!/bin/bash
 # Build an A/B variant of libmlamg_hip.so with extra -D flags on one source (default spmv.hip;
 # SRC=batch.hip for another, SRC_PATH=<file> to compile a different copy of it); the other
-# objects are the in-tree build's. Knobs of the format builders need SRC=formats.hip.
+# objects are the in-tree build's. Knobs of the format builders need SRC=formats.hip, knobs of
+# the batched solver's host planner SRC=batch_plan.cpp (host-only code: the -x hip below compiles
+# it as a HIP source with no kernels, which builds and links like the in-tree object).
 # Timing runs pick it with MLAMG_LIB=<out>:
 #   tools/build_variant.sh tools/variants/libmlamg_w6.so -DMLAMG_RP_WAVES=6
 set -eu
