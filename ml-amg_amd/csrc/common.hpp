@@ -390,28 +390,4 @@ int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStr
 int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s);
 int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X, int64_t ldx,
                    int k, double* ytmp, hipStream_t s);
-// Cycles are launched in batches; with a tolerance, the device-side stop flag is read back
-// after each batch so the cycles after convergence are not launched at all (each would only
-// check the flag and return, ~10 launches apiece). Batches grow 4, 4, 8, 16, 32, 32, ...: at
-// most one batch of overshoot, a host sync per batch.
-template <class F>
-static int run_cycles(int n_cycles, double tol, int32_t* done_dev, int32_t* done_host,
-                      hipStream_t s, F&& one) {
-  if (!(tol >= 0.0) || !done_host) {
-    for (int c = 0; c < n_cycles; ++c) MLAMG_TRY(one());
-    return MLAMG_OK;
-  }
-  int c = 0, batch = 4, k = 0;
-  while (c < n_cycles) {
-    const int m = std::min(batch, n_cycles - c);
-    for (int i = 0; i < m; ++i) MLAMG_TRY(one());
-    c += m;
-    if (c >= n_cycles) break;
-    MLAMG_HIP(hipMemcpyAsync(done_host, done_dev, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    MLAMG_HIP(hipStreamSynchronize(s));
-    if (*done_host) break;
-    if (++k >= 2) batch = std::min(batch * 2, 32);
-  }
-  return MLAMG_OK;
-}
 }  // namespace mlamg

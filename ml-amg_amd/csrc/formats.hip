@@ -1050,7 +1050,7 @@ static int build_rowpat(mlamg_csr* A, hipStream_t s) {
         }
       } else {
         // rows in stored but not ascending column order (a partitioned operator whose ghost
-        // columns follow the owned ones, csrc/comm.hip): the shortest merge that keeps each
+        // columns follow the owned ones, csrc/dhier.hip): the shortest merge that keeps each
         // row's stored order, sharing one 16-byte load where both rows have the same offset
         // (longest common subsequence of the two offset sequences)
         const size_t a = o0.size(), b = o1.size();
@@ -1155,7 +1155,7 @@ static int build_rowpat(mlamg_csr* A, hipStream_t s) {
       }
       return ok;
     };
-    // alternate far offsets (a row-partitioned slab, csrc/comm.hip's x_ext = [owned | ghosts]):
+    // alternate far offsets (a row-partitioned slab, csrc/dhier.hip's x_ext = [owned | ghosts]):
     // a ghost plane's entries reach x at an offset of their own (+n_own for the plane below,
     // +2F for the plane above when the plane below precedes it), unsorted in the row where the
     // plane below comes first. An extra far offset e stands for one of the two far offsets

@@ -13,6 +13,7 @@
 // x = Dinv_w b (0 + d*(b - A@0) bit for bit). The tolerance test runs on the device: the norm
 // kernel raises a flag and every later kernel of the call returns immediately, so a whole batch
 // of cycles is launched (or replayed from one captured hipGraph) without host round trips.
+#include "cycle.hpp"
 #include "formats.hpp"
 
 #include <hip/hip_runtime.h>
@@ -65,21 +66,15 @@ struct mlamg_hier {
   double* partial = nullptr;
   int32_t* flags = nullptr;  // [0] counter, [1] done
   bool ready = false;
-  // captured single cycle
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  const double* g_b = nullptr;
-  double* g_x = nullptr;
-  double* g_hist = nullptr;
-  double g_tol = -1.0;
-  hipStream_t cap_stream = nullptr;
-  // captured coarse cycle (distributed executor: this hierarchy = replicated levels 1..L)
-  hipGraph_t cgraph = nullptr;
-  hipGraphExec_t cexec = nullptr;
-  const double* cg_b = nullptr;
-  uint64_t g_epoch = 0, cg_epoch = 0;
-  double* cg_res = nullptr;
-  int32_t* done_host = nullptr;  // pinned copy of flags[1], polled between batches of cycles
+  // captured single cycle (mlamg_hier_vcycle), and captured zero-guess cycle with level 0 as a
+  // coarse level (hier_coarse_cycle: a Krylov preconditioner, or the distributed executor's
+  // replicated levels). Each is re-keyed on its own; a setter that changes the cycle drops both
+  mlamg::CycleGraph top_graph, coarse_graph;
+  void invalidate_graphs() {
+    top_graph.invalidate();
+    coarse_graph.invalidate();
+  }
+  mlamg::DoneHost done_host;  // pinned copy of flags[1], polled between batches of cycles
   // the stop flag the cycle's kernels test: flags + 1, or nullptr while a no-tolerance
   // mlamg_hier_vcycle runs (nothing can raise it, and every kernel would otherwise start with a
   // dependent load of it). done_check = 1 keeps it on every launch (A/B, mlamg_hier_set_done_check)
@@ -99,17 +94,6 @@ struct mlamg_hier {
 
 
 using namespace mlamg;
-
-static void hier_free_graph(mlamg_hier* H) {
-  if (H->exec) (void)hipGraphExecDestroy(H->exec);
-  if (H->graph) (void)hipGraphDestroy(H->graph);
-  H->exec = nullptr;
-  H->graph = nullptr;
-  if (H->cexec) (void)hipGraphExecDestroy(H->cexec);
-  if (H->cgraph) (void)hipGraphDestroy(H->cgraph);
-  H->cexec = nullptr;
-  H->cgraph = nullptr;
-}
 
 static int64_t coarse_rows(const mlamg_hier* H) {
   if (H->D) return H->D->n;
@@ -162,51 +146,48 @@ static int coarse_solve(mlamg_hier* H, const double* b, double* x, const int32_t
   return pcg_solve_impl(H->pcg, b, x, done, s);
 }
 
+// Hands out consecutive 256-byte-aligned blocks of doubles from `base`. With base = nullptr it
+// only measures, so one layout function, run first on nullptr and then on the allocation, both
+// sizes a work buffer and carves it: the two passes cannot get out of step.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  char* here() const { return base ? base + off : nullptr; }
+  double* take(int64_t n) {
+    double* q = reinterpret_cast<double*>(here());
+    off += (sizeof(double) * (size_t)std::max<int64_t>(n, 1) + 255) & ~size_t(255);
+    return q;
+  }
+};
+
+// the layout of H->mem: the level vectors, the coarse pair, the norm partials, then the flags
+// (counter, done) in a last 256-byte block; returns the bytes needed
+static size_t hier_layout(mlamg_hier* H, char* base) {
+  Carver c{base};
+  for (Level& L : H->lv) {
+    L.x = c.take(L.n);  // level 0 also needs it when this hierarchy serves as a coarse cycle
+    L.b = c.take(L.n);
+    L.r = c.take(L.n);
+    L.tmp = c.take(L.n);
+  }
+  const int64_t nc = coarse_rows(H);
+  H->xc = c.take(nc);
+  H->bc = c.take(nc);
+  int64_t maxblk = 1;
+  for (auto& L : H->lv) maxblk = std::max<int64_t>(maxblk, part_capacity(L.A));
+  H->partial = c.take(maxblk);
+  H->flags = reinterpret_cast<int32_t*>(c.here());
+  return c.off + 256;
+}
+
 static int hier_prepare(mlamg_hier* H) {
   if (H->ready) return MLAMG_OK;
   MLAMG_REQUIRE(H->D != nullptr || H->pcg != nullptr || H->gm_inner != nullptr,
                 "coarse solver not set (mlamg_hier_set_coarse / _pcg / _gmres)");
-  size_t total = 0;
-  auto add = [&](int64_t n) {
-    size_t b = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
-    b = (b + 255) & ~size_t(255);
-    total += b;
-    return b;
-  };
-  for (size_t l = 0; l < H->lv.size(); ++l) {
-    const int64_t n = H->lv[l].n;
-    add(n);  // x: level 0 also needs it when this hierarchy serves as a coarse cycle
-    add(n);
-    add(n);
-    add(n);
-  }
-  const int64_t nc = coarse_rows(H);
-  add(nc);
-  add(nc);
-  int64_t maxblk = 1;
-  for (auto& L : H->lv) maxblk = std::max<int64_t>(maxblk, part_capacity(L.A));
-  add(maxblk);
-  total += 256;
+  const size_t total = hier_layout(H, nullptr);
   MLAMG_HIP(hipMalloc(&H->mem, total));
   H->mem_bytes = total;
-  char* p = static_cast<char*>(H->mem);
-  auto take = [&](int64_t n) {
-    double* q = reinterpret_cast<double*>(p);
-    size_t b = sizeof(double) * (size_t)std::max<int64_t>(n, 1);
-    p += (b + 255) & ~size_t(255);
-    return q;
-  };
-  for (size_t l = 0; l < H->lv.size(); ++l) {
-    Level& L = H->lv[l];
-    L.x = take(L.n);
-    L.b = take(L.n);
-    L.r = take(L.n);
-    L.tmp = take(L.n);
-  }
-  H->xc = take(nc);
-  H->bc = take(nc);
-  H->partial = take(maxblk);
-  H->flags = reinterpret_cast<int32_t*>(p);
+  hier_layout(H, static_cast<char*>(H->mem));
   H->cur_done = H->flags + 1;
   MLAMG_HIP(hipMemset(H->mem, 0, total));
   // hipMemset runs on the null stream and may return before it completes: a caller on a
@@ -227,10 +208,38 @@ static int smooth(const Level& L, const double* b, double*& cur, double* other, 
   return MLAMG_OK;
 }
 
+static int cycle_coarse(mlamg_hier* H, size_t l, const double* b, double** res, hipStream_t s,
+                        bool presmoothed = false);
+
+// What every level does after its pre-smoothing left the iterate in `cur` (x or L.tmp, the
+// ping-pong pair of level l) and b - A cur in L.r: restrict (writing the next level's first
+// zero-guess sweep too when that level takes it), cycle below, prolong, post-smooth. The buffer
+// of the pair that holds the result is returned through `res`.
+static int correct_and_postsmooth(mlamg_hier* H, size_t l, const double* b, double* x,
+                                  double* cur, double** res, hipStream_t s) {
+  const int32_t* done = H->cur_done;
+  Level& L = H->lv[l];
+  const bool last = l + 1 == H->lv.size();
+  const bool fuse_next = !last && H->nu_pre > 0 && !H->lv[l + 1].gs;
+  double* bn = last ? H->bc : H->lv[l + 1].b;
+  if (fuse_next) {
+    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s, H->lv[l + 1].x, H->lv[l + 1].dinv));
+  } else {
+    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s));
+  }
+  double* xn = nullptr;
+  MLAMG_TRY(cycle_coarse(H, l + 1, bn, &xn, s, fuse_next));
+  MLAMG_TRY(prolong_add(L, xn, cur, done, s));
+  double* other = (cur == x) ? L.tmp : x;
+  MLAMG_TRY(smooth(L, b, cur, other, H->nu_post, done, s));
+  *res = cur;
+  return MLAMG_OK;
+}
+
 // one V-cycle below the finest level; result pointer returned through `res`. presmoothed: the
 // caller's restriction kernel already wrote the first zero-guess sweep x = Dinv_w b into L.x.
 static int cycle_coarse(mlamg_hier* H, size_t l, const double* b, double** res, hipStream_t s,
-                        bool presmoothed = false) {
+                        bool presmoothed) {
   const int32_t* done = H->cur_done;
   if (l == H->lv.size()) {
     MLAMG_TRY(coarse_solve(H, b, H->xc, done, s));
@@ -254,20 +263,7 @@ static int cycle_coarse(mlamg_hier* H, size_t l, const double* b, double** res, 
     MLAMG_HIP(hipMemsetAsync(cur, 0, sizeof(double) * L.n, s));
     MLAMG_HIP(hipMemcpyAsync(L.r, b, sizeof(double) * L.n, hipMemcpyDeviceToDevice, s));
   }
-  const bool fuse_next = l + 1 < H->lv.size() && H->nu_pre > 0 && !H->lv[l + 1].gs;
-  double* bn = (l + 1 < H->lv.size()) ? H->lv[l + 1].b : H->bc;
-  if (fuse_next) {
-    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s, H->lv[l + 1].x, H->lv[l + 1].dinv));
-  } else {
-    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s));
-  }
-  double* xn = nullptr;
-  MLAMG_TRY(cycle_coarse(H, l + 1, bn, &xn, s, fuse_next));
-  MLAMG_TRY(prolong_add(L, xn, cur, done, s));
-  other = (cur == L.x) ? L.tmp : L.x;
-  MLAMG_TRY(smooth(L, b, cur, other, H->nu_post, done, s));
-  *res = cur;
-  return MLAMG_OK;
+  return correct_and_postsmooth(H, l, b, L.x, cur, res, s);
 }
 
 // Fused mode (nu_pre >= 1 and an odd number of ping-pong sweeps after the first one, i.e.
@@ -306,18 +302,7 @@ static int cycle_top(mlamg_hier* H, const double* b, double* x, double* hist, do
     MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, done, kNoTol, nullptr,
                             nullptr, nullptr, s));
   }
-  const bool fuse_next = H->lv.size() > 1 && H->nu_pre > 0 && !H->lv[1].gs;
-  double* bn = H->lv.size() > 1 ? H->lv[1].b : H->bc;
-  if (fuse_next) {
-    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s, H->lv[1].x, H->lv[1].dinv));
-  } else {
-    MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s));
-  }
-  double* xn = nullptr;
-  MLAMG_TRY(cycle_coarse(H, 1, bn, &xn, s, fuse_next));
-  MLAMG_TRY(prolong_add(L, xn, cur, done, s));
-  other = (cur == x) ? L.tmp : x;
-  MLAMG_TRY(smooth(L, b, cur, other, H->nu_post, done, s));
+  MLAMG_TRY(correct_and_postsmooth(H, 0, b, x, cur, &cur, s));
   // end-of-cycle residual + norm (+ copy the iterate back into x when it sits in tmp)
   if (H->norm_mode == 1) {  // history of ||x||_2 (amg_2_v error_tol): residual kept for reuse
     MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, done, 0.0,
@@ -359,30 +344,14 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
                       hipStream_t s) {
   MLAMG_TRY(hier_prepare(H));
   if (!use_graph || host_driven_coarse(H)) return cycle_coarse(H, 0, b, x_out, s);
-  if (!(H->cexec && H->cg_b == b && H->cg_epoch == format_epoch())) {
-    if (H->cexec) (void)hipGraphExecDestroy(H->cexec);
-    if (H->cgraph) (void)hipGraphDestroy(H->cgraph);
-    H->cexec = nullptr;
-    H->cgraph = nullptr;
-    if (!H->cap_stream) MLAMG_HIP(hipStreamCreateWithFlags(&H->cap_stream, hipStreamNonBlocking));
-    MLAMG_HIP(hipStreamBeginCapture(H->cap_stream, hipStreamCaptureModeThreadLocal));
-    double* res = nullptr;
-    int rc = cycle_coarse(H, 0, b, &res, H->cap_stream);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(H->cap_stream, &g);
-    if (rc != MLAMG_OK) {
-      if (g) (void)hipGraphDestroy(g);
-      return rc;
-    }
-    MLAMG_HIP(e);
-    H->cgraph = g;
-    MLAMG_HIP(hipGraphInstantiate(&H->cexec, g, nullptr, nullptr, 0));
-    H->cg_b = b;
-    H->cg_epoch = format_epoch();
-    H->cg_res = res;
-  }
-  MLAMG_HIP(hipGraphLaunch(H->cexec, s));
-  *x_out = H->cg_res;
+  CycleGraph& G = H->coarse_graph;
+  CycleKey key;
+  key.b = b;
+  key.epoch = format_epoch();
+  if (!G.current(key))
+    MLAMG_TRY(G.capture(key, [&](hipStream_t cs) { return cycle_coarse(H, 0, b, &G.res, cs); }));
+  MLAMG_TRY(G.launch(s));
+  *x_out = G.res;
   return MLAMG_OK;
 }
 }  // namespace mlamg
@@ -414,30 +383,13 @@ static int mv_unsupported(const char* why) {
   return MLAMG_EUNSUPPORTED;
 }
 
-static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
+// the layout of H->mv_mem: k-wide level blocks (level 0 iterates in the caller's X and reads the
+// caller's B), then the coarse blocks; returns the bytes needed
+static size_t mv_layout(const mlamg_hier* H, int k, MvWork* W, char* base) {
+  Carver c{base};
+  auto take = [&](int64_t n) { return c.take(std::max<int64_t>(n, 1) * k); };
   const size_t nl = H->lv.size();
   const int64_t nc = coarse_rows(H);
-  auto sz = [&](int64_t n) {
-    size_t b = sizeof(double) * (size_t)std::max<int64_t>(n, 1) * (size_t)k;
-    return (b + 255) & ~size_t(255);
-  };
-  size_t total = 0;
-  for (size_t l = 0; l < nl; ++l) total += (l > 0 ? 4 : 2) * sz(H->lv[l].n);
-  total += 3 * sz(nc);
-  if (nl == 0) total += sz(nc);
-  if (H->mv_bytes < total) {
-    if (H->mv_mem) (void)hipFree(H->mv_mem);  // ordered after every earlier use (cache semantics)
-    H->mv_mem = nullptr;
-    H->mv_bytes = 0;
-    MLAMG_HIP(hipMalloc(&H->mv_mem, total));
-    H->mv_bytes = total;
-  }
-  char* p = static_cast<char*>(H->mv_mem);
-  auto take = [&](int64_t n) {
-    double* q = reinterpret_cast<double*>(p);
-    p += sz(n);
-    return q;
-  };
   W->lv.resize(nl);
   for (size_t l = 0; l < nl; ++l) {
     if (l > 0) {
@@ -452,6 +404,19 @@ static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
   W->yc = take(nc);
   if (nl == 0) W->r0 = take(nc);
   W->k = k;
+  return c.off;
+}
+
+static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
+  const size_t total = mv_layout(H, k, W, nullptr);
+  if (H->mv_bytes < total) {
+    if (H->mv_mem) (void)hipFree(H->mv_mem);  // ordered after every earlier use (cache semantics)
+    H->mv_mem = nullptr;
+    H->mv_bytes = 0;
+    MLAMG_HIP(hipMalloc(&H->mv_mem, total));
+    H->mv_bytes = total;
+  }
+  mv_layout(H, k, W, static_cast<char*>(H->mv_mem));
   return MLAMG_OK;
 }
 
@@ -595,10 +560,7 @@ int mlamg_hier_create(mlamg_hier** out) {
 
 int mlamg_hier_destroy(mlamg_hier* H) {
   if (!H) return MLAMG_OK;
-  hier_free_graph(H);
-  if (H->cap_stream) (void)hipStreamDestroy(H->cap_stream);
   if (H->mem) (void)hipFree(H->mem);
-  if (H->done_host) (void)hipHostFree(H->done_host);
   if (H->ws) (void)hipFree(H->ws);
   if (H->zero_b) (void)hipFree(H->zero_b);
   if (H->mv_mem) (void)hipFree(H->mv_mem);
@@ -691,14 +653,14 @@ int mlamg_hier_set_level_smoother(mlamg_hier* H, int level, const mlamg_gs* gs) 
   MLAMG_REQUIRE(H && level >= 0 && (size_t)level < H->lv.size(), "invalid level");
   MLAMG_REQUIRE(!gs || gs_rows(gs) == H->lv[level].n, "Gauss-Seidel handle of another size");
   H->lv[level].gs = gs;
-  hier_free_graph(H);
+  H->invalidate_graphs();
   return MLAMG_OK;
 }
 
 int mlamg_hier_set_norm(mlamg_hier* H, int mode) {
   MLAMG_REQUIRE(H && (mode == 0 || mode == 1), "mode must be 0 (residual) or 1 (x)");
   H->norm_mode = mode;
-  hier_free_graph(H);
+  H->invalidate_graphs();
   return MLAMG_OK;
 }
 
@@ -710,7 +672,7 @@ int mlamg_hier_set_factored_prolong(mlamg_hier* H, int level, const mlamg_csr* A
     L.fac_A = nullptr;
     L.fac_agg = nullptr;
     L.fac_dinv = nullptr;
-    hier_free_graph(H);
+    H->invalidate_graphs();
     return MLAMG_OK;
   }
   MLAMG_REQUIRE(agg && dinv_w, "agg and dinv_w are required");
@@ -722,14 +684,14 @@ int mlamg_hier_set_factored_prolong(mlamg_hier* H, int level, const mlamg_csr* A
   L.fac_A = A_uni;
   L.fac_agg = agg;
   L.fac_dinv = dinv_w;
-  hier_free_graph(H);
+  H->invalidate_graphs();
   return MLAMG_OK;
 }
 
 int mlamg_hier_set_done_check(mlamg_hier* H, int always) {
   MLAMG_REQUIRE(H && (always == 0 || always == 1), "always must be 0 or 1");
   H->done_check = always;
-  hier_free_graph(H);
+  H->invalidate_graphs();
   return MLAMG_OK;
 }
 
@@ -737,7 +699,7 @@ int mlamg_hier_set_smoothing(mlamg_hier* H, int nu_pre, int nu_post) {
   MLAMG_REQUIRE(H && nu_pre >= 0 && nu_post >= 0, "invalid argument");
   H->nu_pre = nu_pre;
   H->nu_post = nu_post;
-  hier_free_graph(H);
+  H->invalidate_graphs();
   return MLAMG_OK;
 }
 
@@ -779,38 +741,16 @@ int mlamg_hier_vcycle(mlamg_hier* H, const double* b, double* x, int n_cycles, d
                             nullptr, nullptr, s));
     if (fused) MLAMG_TRY(jacobi_from_residual(x, L.dinv, L.r, L.n, nullptr, s));
   }
-  if (use_graph && n_cycles > 0 && !H->lv.empty()) {
-    if (!(H->exec && H->g_b == b && H->g_x == x && H->g_hist == res_hist && H->g_tol == tol &&
-          H->g_epoch == format_epoch())) {
-      hier_free_graph(H);
-      if (!H->cap_stream) MLAMG_HIP(hipStreamCreateWithFlags(&H->cap_stream, hipStreamNonBlocking));
-      MLAMG_HIP(hipStreamBeginCapture(H->cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = cycle_top(H, b, x, res_hist, tol, H->cap_stream);
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(H->cap_stream, &g);
-      if (rc != MLAMG_OK) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-      }
-      MLAMG_HIP(e);
-      H->graph = g;
-      MLAMG_HIP(hipGraphInstantiate(&H->exec, g, nullptr, nullptr, 0));
-      H->g_b = b;
-      H->g_x = x;
-      H->g_hist = res_hist;
-      H->g_tol = tol;
-      H->g_epoch = format_epoch();
-    }
-    if (!H->done_host) (void)hipHostMalloc(&H->done_host, sizeof(int32_t), hipHostMallocDefault);
-    MLAMG_TRY(run_cycles(n_cycles, tol, H->flags + 1, H->done_host, s, [&]() -> int {
-      MLAMG_HIP(hipGraphLaunch(H->exec, s));
-      return MLAMG_OK;
-    }));
-  } else {
-    if (!H->done_host) (void)hipHostMalloc(&H->done_host, sizeof(int32_t), hipHostMallocDefault);
-    MLAMG_TRY(run_cycles(n_cycles, tol, H->flags + 1, H->done_host, s,
-                         [&]() { return cycle_top(H, b, x, res_hist, tol, s); }));
+  const bool graph = use_graph && n_cycles > 0 && !H->lv.empty();
+  if (graph) {
+    const CycleKey key{b, x, res_hist, tol, format_epoch()};
+    if (!H->top_graph.current(key))
+      MLAMG_TRY(H->top_graph.capture(
+          key, [&](hipStream_t cs) { return cycle_top(H, b, x, res_hist, tol, cs); }));
   }
+  MLAMG_TRY(run_cycles(n_cycles, tol, H->flags + 1, H->done_host, s, [&]() {
+    return graph ? H->top_graph.launch(s) : cycle_top(H, b, x, res_hist, tol, s);
+  }));
   if (fused)  // the iterate is t (in tmp); x holds t + Dinv_w r for a cycle that never ran
     MLAMG_HIP(hipMemcpyAsync(x, H->lv[0].tmp, sizeof(double) * H->lv[0].n,
                              hipMemcpyDeviceToDevice, s));

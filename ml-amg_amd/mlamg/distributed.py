@@ -1,5 +1,6 @@
 """Multi-GPU V-cycle: the K finest levels row-partitioned over one process per GPU with RCCL halo
-exchanges, the coarser levels replicated (C side: csrc/comm.hip).
+exchanges, the coarser levels replicated (C side: csrc/dhier.hip, the
+executor, over the transport of csrc/comm.hip).
 
 The reference's only parallel backend is a task farm over independent problems
 (ns/parallel/pool.py:139-186: pickled callables over multiprocessing pipes or mpi4py). Splitting
@@ -70,7 +71,7 @@ def comm_info(comm):
 class LoopbackGroup:
     """In-process test transport (include/mlamg.h mlamg_loop_group): `world` communicators whose
     ranks are host threads of this process sharing one GPU, each on its own stream. RCCL refuses
-    two ranks on one device; this runs the distributed executor itself (csrc/comm.hip, eager
+    two ranks on one device; this runs the distributed executor itself (csrc/dhier.hip, eager
     mode) at world sizes > 1 on a single GPU."""
 
     def __init__(self, world):

@@ -1,7 +1,7 @@
 """CPU, world_size 2 and 3 over gloo: the row partition + halo maps of mlamg.partition (the host
 logic the RCCL executor runs on) reproduce the single-process V-cycle bit for bit.
 
-Each rank emulates csrc/comm.hip's distributed cycle step for step with the oracle's arithmetic
+Each rank emulates csrc/dhier.hip's distributed cycle step for step with the oracle's arithmetic
 (scipy csr_matvec order) and torch.distributed (gloo) point-to-point messages in place of RCCL.
 """
 import os
@@ -108,7 +108,7 @@ def _worker(rank, world, port, kind, ncyc, K, q):
             p = parts[l]
             return np.zeros(p["hi"] - p["lo"] + max(p["halo_x"].n_ghost, p["halo_r"].n_ghost))
 
-        # emulation of csrc/comm.hip: correct / dcycle_below / dcycle
+        # emulation of csrc/dhier.hip: correct / dcycle_below / dcycle
         def correct(l, r):
             p = parts[l]
             m = p["hi"] - p["lo"]

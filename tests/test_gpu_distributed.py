@@ -1,4 +1,4 @@
-"""GPU, one rank: the RCCL distributed executor (csrc/comm.hip) with 1..all levels partitioned
+"""GPU, one rank: the RCCL distributed executor (csrc/dhier.hip) with 1..all levels partitioned
 reproduces the single-GPU V-cycle bit for bit (the multi-rank maps are covered by the gloo
 emulation in test_distributed_gloo.py)."""
 import numpy as np
@@ -57,6 +57,72 @@ def test_distributed_tolerance_stop(setup):
         h = D.cycle(b, xe, 50, tol=1e-6 * float(torch.linalg.norm(b)))
         assert len(h) == len(h_ref) < 50
         assert torch.equal(xe[:n], x)
+
+
+def test_cached_graphs_survive_changes_to_the_replicated_hierarchy(setup):
+    """One executor with both of its graphs cached (the whole-cycle graph of the mlamg_dhier, the
+    zero-guess graph of its replicated tail) keeps computing the eager bits while the replicated
+    hierarchy it shares operators with is used and changed in between: a captured cycle of H
+    itself, set_smoothing to the same values (drops a hierarchy's graphs), and a set_format of a
+    tail operator (format epoch: every cached graph is stale). The same three on the executor's
+    own tail handle, whose top-level graph is re-keyed while its zero-guess graph is in use."""
+    from mlamg import problems
+    from mlamg._lib import call, ptr, stream_ptr
+    from mlamg.distributed import DistributedHierarchy
+    from mlamg.hierarchy import Hierarchy
+    _, _, comm = setup
+    A = problems.poisson_3d_7pt(20)
+    n = A.shape[0]
+    H = Hierarchy.build(A, alpha=0.1, max_coarse=100, coarse_format="exact")
+    D = DistributedHierarchy(H, comm, min_rows=10**9, A_host=A)
+    assert D.K == 1 and len(H.levels) == 2  # the tail is one level and the coarse solve
+    rs = np.random.RandomState(5)
+    x0 = torch.as_tensor(rs.randn(n))
+    b = torch.as_tensor(rs.randn(n)).cuda()
+    xe = D.new_x(x0)
+    hist = torch.zeros(5, dtype=torch.float64, device="cuda")
+
+    def cycle():  # same b, x and history buffers every time: the executor's graph key holds
+        xe[:n].copy_(x0)
+        hist.zero_()
+        call("mlamg_dhier_vcycle", D.handle, ptr(b), ptr(xe), 5, -1.0, ptr(hist), None,
+             stream_ptr())
+        return xe[:n].clone(), hist.cpu().numpy()
+
+    D.set_coarse_graph(False)
+    D.set_cycle_graph(False)
+    x_ref, h_ref = cycle()  # the eager executor, itself bitwise the single-GPU iterate
+    x_single = x0.cuda()
+    H.cycle(b, x_single, 5, use_graph=False)
+    assert torch.equal(x_ref, x_single)
+
+    def check(what):
+        x, h = cycle()
+        assert torch.equal(x, x_ref) and np.array_equal(h, h_ref), what
+
+    n1 = H.levels[1].A.shape[0]
+    b1 = torch.as_tensor(rs.randn(n1)).cuda()
+
+    def tail_cycle(handle, nb):  # a captured top-level cycle on a hierarchy handle
+        x = torch.zeros(nb, dtype=torch.float64, device="cuda")
+        rhs = b if nb == n else b1
+        call("mlamg_hier_vcycle", handle, ptr(rhs), ptr(x), 2, -1.0, None, None, 1, stream_ptr())
+
+    for coarse_graph, cycle_graph in ((True, True), (True, False)):
+        D.set_coarse_graph(coarse_graph)
+        D.set_cycle_graph(cycle_graph)
+        check("first")
+        check("replay")
+        tail_cycle(H.handle, n)
+        check("after a captured cycle of H")
+        call("mlamg_hier_set_smoothing", H.handle, 1, 1)
+        check("after H.set_smoothing")
+        tail_cycle(D.coarse, n1)
+        check("after a captured top-level cycle of the tail")
+        call("mlamg_hier_set_smoothing", D.coarse, 1, 1)
+        check("after set_smoothing on the tail")
+        H.levels[1].A.set_format("csr_stream" if cycle_graph else "sell")
+        check("after set_format")
 
 
 def test_finalize_replicated_matches_full_build():

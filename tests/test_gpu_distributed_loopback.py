@@ -1,11 +1,11 @@
-"""GPU, one process, world sizes 2, 3 and 8: the distributed executor of csrc/comm.hip — halo
+"""GPU, one process, world sizes 2, 3 and 8: the distributed executor of csrc/dhier.hip — halo
 packs and exchanges, restriction into owned coarse rows, P-halos aliased to the level below's
 buffers, the allgather of coarse segments, the replicated coarse cycle, the norm all-reduce —
 run with every rank a host thread on its own stream of the same GPU, over the in-process loopback
 transport (mlamg_loop_group; RCCL refuses two ranks on one device). Every rank's owned iterate
 must equal the single-GPU iterate bit for bit, and the residual history must agree (only the
 norm's summation order differs). The RCCL calls themselves are the loopback's counterparts, one
-for one (xsend/xrecv/xgroup_*/xallreduce_sum in comm.hip)."""
+for one (xsend/xrecv/xgroup_*/xallreduce_sum, comm.hip's transport)."""
 import threading
 
 import numpy as np

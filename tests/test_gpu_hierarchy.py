@@ -408,6 +408,51 @@ def test_graph_recaptured_after_format_change(ml, torch_cuda):
         assert np.allclose(h, h_ref, rtol=1e-14, atol=0)
 
 
+def test_graph_rekeyed_by_every_argument(ml, torch_cuda):
+    """A captured cycle bakes in b, x, the history buffer and the tolerance: a call that differs
+    in any one of them must re-capture, and a call with the first arguments must not replay a
+    later capture. The buffers are held here (Hierarchy.cycle would hand the library a fresh
+    history tensor per call), so each step changes exactly one key field. Every iterate is
+    bitwise the eager run of the same call, every history equal to it."""
+    torch = torch_cuda
+    from mlamg._lib import call, ptr, stream_ptr
+    A = ml.problems.poisson_3d_7pt(20)
+    n = A.shape[0]
+    rs = np.random.RandomState(11)
+    x0 = dev(torch, rs.randn(n))
+    b1, b2 = dev(torch, rs.randn(n)), dev(torch, rs.randn(n))
+    H = ml.hierarchy.Hierarchy.build(A, alpha=0.1, max_coarse=100, coarse_format="exact")
+    nc = 6
+
+    def run(b, x, hist, tol, use_graph):
+        x.copy_(x0)
+        if hist is not None:
+            hist.zero_()
+        done = ctypes.c_int32()
+        call("mlamg_hier_vcycle", H.handle, ptr(b), ptr(x), nc, -1.0 if tol is None else tol,
+             ptr(hist), ctypes.byref(done), int(use_graph), stream_ptr())
+        return x.clone(), None if hist is None else hist[: done.value].cpu().numpy()
+
+    xa, xb, xe = (torch.empty_like(x0) for _ in range(3))
+    ha, he = (torch.zeros(nc, dtype=torch.float64, device="cuda") for _ in range(2))
+    tol = float(run(b2, xe, he, None, False)[1][2])  # stops the b2 run after its third cycle
+    first = (b1, xa, ha, None)
+    steps = [first,
+             (b2, xa, ha, None),     # another b
+             (b2, xb, ha, None),     # another x
+             (b2, xb, None, None),   # no history
+             (b2, xb, ha, tol),      # a tolerance
+             (None, xb, ha, tol),    # a zero right-hand side
+             first]
+    for i, (b, x, hist, t) in enumerate(steps):
+        x_ref, h_ref = run(b, xe, None if hist is None else he, t, False)
+        x_got, h_got = run(b, x, hist, t, True)
+        assert torch.equal(x_got, x_ref), i
+        if hist is not None:
+            assert np.array_equal(h_got, h_ref), i
+    assert len(run(b2, xb, ha, tol, True)[1]) == 3
+
+
 def test_sell_dict_format(ml, torch_cuda):
     """Dictionary-coded SELL: bitwise CSR order on a stencil (ragged boundary rows, sigma
     orders), every epilogue through the hierarchy, and refusal past 255 offsets / 256 values."""

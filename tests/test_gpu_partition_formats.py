@@ -1,6 +1,6 @@
 """GPU, one process: every rank's LOCAL operators of the multi-GPU partition (A_loc with ghost
 columns, P_loc over owned + x-ghost rows, R_own with r-ghost columns — mlamg.partition.build_levels,
-the maps csrc/comm.hip runs on) through every SpMV storage format, bitwise against scipy's
+the maps csrc/dhier.hip runs on) through every SpMV storage format, bitwise against scipy's
 csr_matvec order (the oracle's vector order for 'vector').
 
 RCCL refuses two ranks on one GPU, so the driver's 8-GPU run is the first to execute the real
