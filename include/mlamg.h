@@ -613,11 +613,33 @@ int mlamg_dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, dou
  * every cycle (ns/model/loss.py:89; ns/lib/multigrid.py:186-187). hist (DEVICE, n_cycles x k
  * row-major, nullable) receives after each cycle, per column, ||b - A x||_2 (norm_mode 0) or
  * ||x||_2 (norm_mode 1), taken after the mean removal. A fixed cycle count (no tolerance stop),
- * run eagerly. MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother, a PCG or GMRES coarse
- * solve, a factored prolongation, or any operator in the VECTOR format. */
+ * run eagerly. The coarsest solve is the dense inverse (mlamg_dense_solve_mv) or the block PCG
+ * (mlamg_pcg_solve_mv; a breakdown is counted in the solver's statistics, not returned).
+ * MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother, a GMRES coarse solve, a factored
+ * prolongation, or any operator in the VECTOR format. */
 int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
                          int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
                          void* stream);
+
+/* X = A^-1 B by PCG on the n_c x k block (B, X) (multivectors as above; B != X): the iteration
+ * of mlamg_pcg_solve on every column at once, the operator and the preconditioner's hierarchy
+ * streamed once per iteration for all k columns. COLUMN j OF X AND COLUMN j'S ITERATION COUNT
+ * ARE BITWISE WHAT mlamg_pcg_solve GIVES ON COLUMN j ALONE: every dot product keeps the single
+ * kernel's partition and summation order per column, and the updates round as the single
+ * kernels do. Each column has its own scalars, done flag and iteration counter; a column that
+ * has converged, has a zero right-hand side or broke down (p.Ap <= 0, r.z <= 0 or a NaN) is
+ * frozen (its x, r and p are no longer written) while the others continue. The host polls an
+ * all-columns-done flag as mlamg_pcg_solve polls its done flag; inside a stream capture all
+ * maxit iterations are recorded. The cumulative statistics (mlamg_pcg_stats,
+ * mlamg_pcg_breakdowns) afterwards read as after k single solves, column 0 first. The n_c x k
+ * work blocks are owned by the solver and grown on demand (not capture-safe on first use of a
+ * larger k). MLAMG_EUNSUPPORTED where the preconditioner's hierarchy has no block cycle (see
+ * mlamg_hier_vcycle_mv; its coarsest solve must be dense). Not reentrant on one solver. */
+int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                       void* stream);
+/* iters[j] (HOST, k entries) = iterations column j took in the last mlamg_pcg_solve_mv (k at
+ * most that call's k); syncs */
+int mlamg_pcg_iters_mv(const mlamg_pcg* C, int32_t* iters, int k, void* stream);
 
 /* Sampled dense-dense product on S's pattern (csrc/sddmm.hip; the gradient of amg_loss with
  * respect to a prolongator's stored values, mlamg/loss.py):

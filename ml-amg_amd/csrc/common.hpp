@@ -358,6 +358,17 @@ int pcg_solve_impl(mlamg_pcg* C, const double* b, double* x, const int32_t* oute
                    hipStream_t s);
 int64_t pcg_rows(const mlamg_pcg* C);
 mlamg_hier* pcg_inner(mlamg_pcg* C);
+// the same solve on the n_c x k block (B -> X), per column the bits of pcg_solve_impl on that
+// column (arguments already validated)
+int pcg_solve_mv_impl(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                      hipStream_t s);
+// hier_coarse_cycle on a block: one zero-guess cycle of H with its level 0 as a coarse level on
+// the n x k block B (leading dimension k); *X_out (leading dimension k) lies in H's block
+// workspace. done (nullable): a device flag that turns every launch of the cycle into a no-op
+// once it is raised. MLAMG_EUNSUPPORTED where mlamg_hier_vcycle_mv refuses, and for a coarsest
+// solve that is not dense.
+int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
+                         const int32_t* done = nullptr);
 // restarted left-preconditioned GMRES (scipy's algorithm) with one V-cycle of M as
 // preconditioner (gmres.hip); rel_out (optional): final ||b - A x|| / ||b||
 int gmres_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, double* x, double rtol,
@@ -373,21 +384,23 @@ int norm_hist_impl(const double* x, int64_t n, double* partial, double* hist, in
 int count_out_of_range(const int32_t* a, int64_t n, int64_t lo, int64_t hi, hipStream_t s,
                        int64_t* bad_out);
 // multi-vector (row-major n x k, leading dimension ld) building blocks of the block V-cycle
-// (spmm.hip); per column the bits of the single-vector functions above
+// (spmm.hip); per column the bits of the single-vector functions above. done (nullable): a
+// device flag; once it is raised the launch does nothing (the block PCG's all-columns-done flag,
+// the single path's stop flag on a block)
 int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                double alpha, double beta, hipStream_t s);
+                double alpha, double beta, hipStream_t s, const int32_t* done = nullptr);
 int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                hipStream_t s);
+                hipStream_t s, const int32_t* done = nullptr);
 int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
-                double* R, int64_t ldr, int k, hipStream_t s);
+                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done = nullptr);
 int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
                     const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
-                    hipStream_t s);
+                    hipStream_t s, const int32_t* done = nullptr);
 // mode 0: X += d .* R (jacobi_from_residual), mode 1: X = d .* R (jacobi_from_zero)
 int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ldr, int64_t n,
-            int k, int mode, hipStream_t s);
+            int k, int mode, hipStream_t s, const int32_t* done = nullptr);
 int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStream_t s);
 int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s);
 int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X, int64_t ldx,
-                   int k, double* ytmp, hipStream_t s);
+                   int k, double* ytmp, hipStream_t s, const int32_t* done = nullptr);
 }  // namespace mlamg

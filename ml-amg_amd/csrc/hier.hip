@@ -361,7 +361,8 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
 // multi-vector kernels of spmm.hip. The fusions of the single path (first sweep written by the
 // restriction or the end-of-cycle residual kernel) are left out: they are the same roundings, so
 // column j keeps the bits of the single-vector cycle on column j. Work buffers are k-wide copies
-// of the level vectors with leading dimension k.
+// of the level vectors with leading dimension k. The coarsest solve is the dense inverse or the
+// block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner hierarchy.
 namespace {
 struct MvLevel {
   double* x = nullptr;    // l > 0: iterate
@@ -376,26 +377,44 @@ struct MvWork {
   double* yc = nullptr;  // dense method 2: the intermediate X b
   double* r0 = nullptr;  // coarse-only hierarchy: residual of the history
   int k = 0;
+  const int32_t* done = nullptr;  // stop flag of every launch (hier_coarse_cycle_mv's caller's)
 };
 
-static int mv_unsupported(const char* why) {
-  set_error(std::string("mlamg_hier_vcycle_mv: ") + why);
+static int mv_unsupported(const char* why, const char* who = "mlamg_hier_vcycle_mv") {
+  set_error(std::string(who) + ": " + why);
   return MLAMG_EUNSUPPORTED;
 }
 
+// what the block cycle cannot run (MLAMG_EUNSUPPORTED, the message names it); pcg_ok: a PCG
+// coarsest solve is taken (the block PCG), else the coarsest solve must be the dense inverse
+static int mv_refusals(const mlamg_hier* H, bool pcg_ok, const char* who) {
+  if (H->pcg && !pcg_ok)
+    return mv_unsupported("the coarse solve is PCG (dense coarse solves only)", who);
+  if (H->gm_inner)
+    return mv_unsupported("the coarse solve is GMRES (dense coarse solves only)", who);
+  for (const Level& L : H->lv) {
+    if (L.gs)
+      return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)", who);
+    if (L.fac_A) return mv_unsupported("a level uses a factored prolongation", who);
+    if (L.A->vec_width || L.P->vec_width || L.R->vec_width)
+      return mv_unsupported("an operator is in the VECTOR format, whose row order is not scipy's",
+                            who);
+  }
+  return MLAMG_OK;
+}
+
 // the layout of H->mv_mem: k-wide level blocks (level 0 iterates in the caller's X and reads the
-// caller's B), then the coarse blocks; returns the bytes needed
-static size_t mv_layout(const mlamg_hier* H, int k, MvWork* W, char* base) {
+// caller's B; as a coarse level, hier_coarse_cycle_mv, it has an iterate of its own: level0_x),
+// then the coarse blocks; returns the bytes needed
+static size_t mv_layout(const mlamg_hier* H, int k, MvWork* W, char* base, bool level0_x) {
   Carver c{base};
   auto take = [&](int64_t n) { return c.take(std::max<int64_t>(n, 1) * k); };
   const size_t nl = H->lv.size();
   const int64_t nc = coarse_rows(H);
   W->lv.resize(nl);
   for (size_t l = 0; l < nl; ++l) {
-    if (l > 0) {
-      W->lv[l].x = take(H->lv[l].n);
-      W->lv[l].b = take(H->lv[l].n);
-    }
+    if (l > 0 || level0_x) W->lv[l].x = take(H->lv[l].n);
+    if (l > 0) W->lv[l].b = take(H->lv[l].n);
     W->lv[l].r = take(H->lv[l].n);
     W->lv[l].tmp = take(H->lv[l].n);
   }
@@ -407,8 +426,8 @@ static size_t mv_layout(const mlamg_hier* H, int k, MvWork* W, char* base) {
   return c.off;
 }
 
-static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
-  const size_t total = mv_layout(H, k, W, nullptr);
+static int mv_workspace(mlamg_hier* H, int k, MvWork* W, bool level0_x = false) {
+  const size_t total = mv_layout(H, k, W, nullptr, level0_x);
   if (H->mv_bytes < total) {
     if (H->mv_mem) (void)hipFree(H->mv_mem);  // ordered after every earlier use (cache semantics)
     H->mv_mem = nullptr;
@@ -416,26 +435,35 @@ static int mv_workspace(mlamg_hier* H, int k, MvWork* W) {
     MLAMG_HIP(hipMalloc(&H->mv_mem, total));
     H->mv_bytes = total;
   }
-  mv_layout(H, k, W, static_cast<char*>(H->mv_mem));
+  mv_layout(H, k, W, static_cast<char*>(H->mv_mem), level0_x);
   return MLAMG_OK;
 }
 
 static int smooth_mv(const Level& L, const double* B, int64_t ldb, double*& cur, int64_t& lc,
-                     double*& other, int64_t& lo, int nu, int k, hipStream_t s) {
+                     double*& other, int64_t& lo, int nu, int k, hipStream_t s,
+                     const int32_t* done = nullptr) {
   for (int i = 0; i < nu; ++i) {
-    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s));
+    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s, done));
     std::swap(cur, other);
     std::swap(lc, lo);
   }
   return MLAMG_OK;
 }
 
+// the coarsest solve on a block: dense inverse, or the block PCG (pcg.hip) on H's PCG solver
+static int coarse_solve_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
+                           int k, double* ytmp, hipStream_t s, const int32_t* done) {
+  if (H->D) return dense_solve_mv(H->D, B, ldb, X, ldx, k, ytmp, s, done);
+  return pcg_solve_mv_impl(H->pcg, B, ldb, X, ldx, k, s);
+}
+
 // one V-cycle below the finest level from a zero guess (cycle_coarse); every block has ld = k
 static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, double** res,
                            hipStream_t s) {
   const int k = W.k;
+  const int32_t* done = W.done;
   if (l == H->lv.size()) {
-    MLAMG_TRY(dense_solve_mv(H->D, B, k, W.xc, k, k, W.yc, s));
+    MLAMG_TRY(coarse_solve_mv(H, B, k, W.xc, k, k, W.yc, s, done));
     *res = W.xc;
     return MLAMG_OK;
   }
@@ -446,24 +474,36 @@ static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, 
   int64_t lc = k, lo = k;
   const size_t bytes = sizeof(double) * (size_t)L.n * (size_t)k;
   if (H->nu_pre > 0) {
-    MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s));
-    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s));
-    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s));
+    MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s, done));
+    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s, done));
+    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done));
   } else {
     MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
     MLAMG_HIP(hipMemcpyAsync(M.r, B, bytes, hipMemcpyDeviceToDevice, s));
   }
   double* bn = (l + 1 < H->lv.size()) ? W.lv[l + 1].b : W.bc;
-  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s));
+  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, done));
   double* xn = nullptr;
   MLAMG_TRY(cycle_coarse_mv(H, W, l + 1, bn, &xn, s));
-  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s));
+  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s, done));
   other = (cur == M.x) ? M.tmp : M.x;
-  MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_post, k, s));
+  MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_post, k, s, done));
   *res = cur;
   return MLAMG_OK;
 }
 }  // namespace
+
+namespace mlamg {
+int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
+                         const int32_t* done) {
+  MLAMG_TRY(mv_refusals(H, false, "block cycle of a Krylov solver's inner hierarchy"));
+  MLAMG_TRY(hier_prepare(H));
+  MvWork W;
+  MLAMG_TRY(mv_workspace(H, k, &W, true));
+  W.done = done;
+  return cycle_coarse_mv(H, W, 0, B, X_out, s);
+}
+}  // namespace mlamg
 
 extern "C" {
 
@@ -476,20 +516,13 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
   MLAMG_REQUIRE(B != X, "B and X must differ");
   MLAMG_REQUIRE(n_cycles >= 0, "n_cycles < 0");
   MLAMG_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode must be 0 (residual) or 1 (x)");
-  if (H->pcg) return mv_unsupported("the coarse solve is PCG (dense coarse solves only)");
-  if (H->gm_inner) return mv_unsupported("the coarse solve is GMRES (dense coarse solves only)");
-  for (const Level& L : H->lv) {
-    if (L.gs) return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)");
-    if (L.fac_A) return mv_unsupported("a level uses a factored prolongation");
-    if (L.A->vec_width || L.P->vec_width || L.R->vec_width)
-      return mv_unsupported("an operator is in the VECTOR format, whose row order is not scipy's");
-  }
+  MLAMG_TRY(mv_refusals(H, true, "mlamg_hier_vcycle_mv"));
   MLAMG_TRY(hier_prepare(H));
   hipStream_t s = S(stream);
   MvWork W;
   MLAMG_TRY(mv_workspace(H, k, &W));
   if (H->lv.empty()) {  // coarse-only hierarchy: X = A^-1 B each cycle
-    const int64_t nc = H->D->n;
+    const int64_t nc = coarse_rows(H);
     if (!B) {
       MLAMG_HIP(hipMemsetAsync(W.bc, 0, sizeof(double) * (size_t)std::max<int64_t>(nc, 1) * k, s));
       B = W.bc;
@@ -498,7 +531,7 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
     if (hist && norm_mode == 0 && !H->Ac)
       return mv_unsupported("a coarse-only hierarchy without its operator has no residual norm");
     for (int c = 0; c < n_cycles; ++c) {
-      MLAMG_TRY(dense_solve_mv(H->D, B, ldb, X, ldx, k, W.yc, s));
+      MLAMG_TRY(coarse_solve_mv(H, B, ldb, X, ldx, k, W.yc, s, nullptr));
       if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, nc, k, s));
       if (hist && norm_mode == 0) {
         MLAMG_TRY(residual_mv(H->Ac, B, ldb, X, ldx, W.r0, k, k, s));

@@ -41,6 +41,16 @@ struct mlamg_pcg {
   int32_t* done_host = nullptr;  // two pinned slots of the polled done flag
   hipEvent_t ev[2] = {nullptr, nullptr};
   int nb = 1;
+  // block solve (mlamg_pcg_solve_mv): n x kcap work blocks with leading dimension k of the call,
+  // grown on demand
+  void* mv_mem = nullptr;
+  int mv_kcap = 0;
+  double *R = nullptr, *P = nullptr, *Q = nullptr;
+  double* mv_partial = nullptr;  // two sets of MLAMG_MV_MAX x kPcgMaxBlocks partials, [col * nb + b]
+  double* mv_scal = nullptr;     // 8 doubles per column, scal's layout
+  int32_t* mv_state = nullptr;   // [0] all columns done, [1] columns done, [2] columns of the last
+                                 // block solve, then per column c: [8 + 2c] done, [9 + 2c]
+                                 // iterations
 };
 
 namespace mlamg {
@@ -345,6 +355,414 @@ __global__ __launch_bounds__(256) void k_sym_check(const int32_t* __restrict__ i
   if (!ok) bad[0] = 1;
 }
 
+// ---------------------------------------------------------------- block (n x k) solve
+// The iteration above on every column of a row-major n x k block at once. Column j keeps the bits
+// of the single solve on column j: the reduction kernels walk the rows exactly as the single
+// kernels do (nb = pcg_grid(n) workgroups of 256 on blockIdx.x, thread t of block b takes the rows
+// b*256 + t + m*nb*256, the wave butterfly, ((red0+red1)+red2)+red3) with one accumulator per
+// column of a tile of kPcgCT columns (blockIdx.y; spmm.hip's k_colsum_partial), partials at
+// [col * nb + b]; the consumer sums a column's partials in last_total's order (col_total: one
+// wave plays the four waves of last_total's workgroup). No arrival counter, as above. Every
+// column has its scalars (scal's layout at sc + 8 col), a done flag and an iteration counter; a
+// done column is frozen (nothing of it is read or written any more). The thread that marks the
+// last column done raises the all-done flag st[0], which the host polls and every launch of the
+// preconditioner's block cycle tests.
+constexpr int kPcgCT = 8;  // columns per thread in the block kernels (spmm.hip kMvCT)
+
+__device__ __forceinline__ int32_t* col_done(int32_t* st, int c) { return st + 8 + 2 * c; }
+__device__ __forceinline__ int32_t* col_iters(int32_t* st, int c) { return st + 9 + 2 * c; }
+
+// marks column c done (called by exactly one thread per column and solve)
+__device__ __forceinline__ void finish_col(int32_t* st, int c, int k) {
+  *col_done(st, c) = 1;
+  if (atomicAdd(st + 1, 1) == k - 1) st[0] = 1;
+}
+
+__device__ __forceinline__ void breakdown_col(int32_t* st, int c, int k, int32_t* flags) {
+  finish_col(st, c, k);
+  atomicAdd(flags + 3, 1);
+}
+
+// largest final relative residual over all solves (a NaN is not recorded, as `rel > scal[5]`);
+// non-negative doubles order as their bit patterns
+__device__ __forceinline__ void record_rel(double* scal, double rel) {
+  if (rel > 0.0)
+    atomicMax(reinterpret_cast<unsigned long long*>(scal + 5),
+              (unsigned long long)__double_as_longlong(rel));
+}
+
+// last_total(partial, nb) computed by one wave: lane l carries the sums of last_total's threads
+// l, l + 64, l + 128, l + 192 (the same strided order), each goes through the same butterfly, and
+// the four wave sums are added in red[]'s order. All lanes get the total.
+__device__ __forceinline__ double col_total(const double* __restrict__ partial, int nb, int lane) {
+  double w[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    w[u] = pcg_wave_sum(strided_sum(partial, nb, lane + 64 * u, kPcgThreads));
+  return ((w[0] + w[1]) + w[2]) + w[3];
+}
+
+// bit c set: column c0 + c of the tile exists and is not done
+__device__ __forceinline__ unsigned live_cols(const int32_t* st, int c0, int nc) {
+  unsigned live = 0;
+  for (int c = 0; c < nc; ++c)
+    if (!st[8 + 2 * (c0 + c)]) live |= 1u << c;
+  return live;
+}
+
+// live_cols, or 0 once every column is done, read by one thread for the whole workgroup: a
+// breakdown marks a column done while other workgroups of the same launch start, and the barriers
+// below need every thread of a workgroup to take the same path
+__device__ __forceinline__ unsigned tile_live(const int32_t* st, int c0, int nc) {
+  __shared__ unsigned s_live;
+  if (threadIdx.x == 0) s_live = st[0] ? 0u : live_cols(st, c0, nc);
+  __syncthreads();
+  return s_live;
+}
+
+// the tile's per-column block sums -> partial[(c0 + c) * gridDim.x + blockIdx.x] (live columns)
+__device__ __forceinline__ void tile_partials(double (&acc)[kPcgCT], unsigned live, int c0,
+                                              double* __restrict__ partial) {
+  __shared__ double red[kPcgThreads / 64][kPcgCT];
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c) {
+    const double w = pcg_wave_sum(acc[c]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
+    const int c = threadIdx.x;
+    partial[(int64_t)(c0 + c) * gridDim.x + blockIdx.x] =
+        ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+  }
+}
+
+// k_pcg_init per column: x = 0, r = b, partials of b.b; every column's state is re-armed
+__global__ __launch_bounds__(kPcgThreads) void k_pcgmv_init(const double* __restrict__ B,
+                                                            int64_t ldb, double* __restrict__ X,
+                                                            int64_t ldx, double* __restrict__ R,
+                                                            int64_t n, int k,
+                                                            double* __restrict__ partial,
+                                                            int32_t* st, int32_t* flags) {
+  const int c0 = blockIdx.y * kPcgCT;
+  const int nc = min(kPcgCT, k - c0);
+  if (blockIdx.x == 0) {
+    if (threadIdx.x < nc) {
+      *col_done(st, c0 + threadIdx.x) = 0;
+      *col_iters(st, c0 + threadIdx.x) = 0;
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+      st[0] = 0;
+      st[1] = 0;
+      st[2] = k;
+      flags[0] = 0;
+    }
+  }
+  double acc[kPcgCT];
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c) acc[c] = 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kPcgThreads) {
+    const double* b = B + i * ldb + c0;
+    double* x = X + i * ldx + c0;
+    double* r = R + i * (int64_t)k + c0;
+#pragma unroll
+    for (int c = 0; c < kPcgCT; ++c) {
+      if (c < nc) {
+        const double v = b[c];
+        x[c] = 0.0;
+        r[c] = v;
+        acc[c] += v * v;
+      }
+    }
+  }
+  tile_partials(acc, (1u << nc) - 1u, c0, partial);
+}
+
+// ||b||^2 of every column (a wave each); a zero right-hand side is solved by x = 0
+__global__ __launch_bounds__(64) void k_pcgmv_bnorm(const double* __restrict__ partial, int nb,
+                                                    int k, double* sc, int32_t* st) {
+  const int c = blockIdx.x;
+  const double t = col_total(partial + (int64_t)c * nb, nb, threadIdx.x);
+  if (threadIdx.x == 0) {
+    sc[8 * c + 3] = t;
+    if (!(t > 0.0)) finish_col(st, c, k);
+  }
+}
+
+// partials of u.v per column (p.q: the alpha step's denominator; r.z)
+__global__ __launch_bounds__(kPcgThreads) void k_pcgmv_dot(const double* __restrict__ U,
+                                                           const double* __restrict__ V,
+                                                           int64_t n, int k,
+                                                           double* __restrict__ partial,
+                                                           const int32_t* st) {
+  const int c0 = blockIdx.y * kPcgCT;
+  const unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  if (!live) return;
+  double acc[kPcgCT];
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c) acc[c] = 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kPcgThreads) {
+    const double* u = U + i * (int64_t)k + c0;
+    const double* v = V + i * (int64_t)k + c0;
+#pragma unroll
+    for (int c = 0; c < kPcgCT; ++c)
+      if ((live >> c) & 1u) acc[c] += u[c] * v[c];
+  }
+  tile_partials(acc, live, c0, partial);
+}
+
+// the totals of the tile's live columns, by the workgroup's four waves (two columns each), left
+// in tot[]; ends with a barrier
+__device__ __forceinline__ void tile_totals(const double* __restrict__ partial, int nb, int c0,
+                                            unsigned live, double (&tot)[kPcgCT]) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int u = 0; u < kPcgCT / 4; ++u) {
+    const int c = w + 4 * u;
+    if ((live >> c) & 1u) {
+      const double t = col_total(partial + (int64_t)(c0 + c) * nb, nb, lane);
+      if (lane == 0) tot[c] = t;
+    }
+  }
+  __syncthreads();
+}
+
+// k_pcg_update per column: alpha = rho / (p.q); x += alpha p, r -= alpha q; partials of r.r
+__global__ __launch_bounds__(kPcgThreads) void k_pcgmv_update(double* __restrict__ X, int64_t ldx,
+                                                              double* __restrict__ R,
+                                                              const double* __restrict__ P,
+                                                              const double* __restrict__ Q,
+                                                              int64_t n, int k, double* sc,
+                                                              const double* __restrict__ pq,
+                                                              double* __restrict__ partial,
+                                                              int32_t* st, int32_t* flags,
+                                                              int it) {
+  __shared__ double tot[kPcgCT];
+  __shared__ double al[kPcgCT];
+  const int c0 = blockIdx.y * kPcgCT;
+  unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  if (!live) return;
+  tile_totals(pq, gridDim.x, c0, live, tot);
+  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
+    const int c = threadIdx.x;
+    const double t = tot[c];
+    const double alpha = sc[8 * (c0 + c) + 6 + (it & 1)] / t;
+    al[c] = alpha;
+    if (blockIdx.x == 0) {
+      if (!(t > 0.0)) {  // p.Ap <= 0 or NaN: A_c not positive definite
+        breakdown_col(st, c0 + c, k, flags);
+      } else {
+        sc[8 * (c0 + c) + 1] = alpha;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c)
+    if (((live >> c) & 1u) && !(tot[c] > 0.0)) live &= ~(1u << c);
+  if (!live) return;
+  double alpha[kPcgCT], acc[kPcgCT];
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c) {
+    alpha[c] = ((live >> c) & 1u) ? al[c] : 0.0;
+    acc[c] = 0.0;
+  }
+  for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kPcgThreads) {
+    double* x = X + i * ldx + c0;
+    double* r = R + i * (int64_t)k + c0;
+    const double* p = P + i * (int64_t)k + c0;
+    const double* q = Q + i * (int64_t)k + c0;
+#pragma unroll
+    for (int c = 0; c < kPcgCT; ++c) {
+      if ((live >> c) & 1u) {
+        x[c] += alpha[c] * p[c];
+        const double v = r[c] - alpha[c] * q[c];
+        r[c] = v;
+        acc[c] += v * v;
+      }
+    }
+  }
+  tile_partials(acc, live, c0, partial);
+}
+
+// k_pcg_check per column (a wave each): ||r||^2 <= rtol^2 ||b||^2 -> the column is done;
+// iteration counts
+__global__ __launch_bounds__(64) void k_pcgmv_check(const double* __restrict__ partial, int nb,
+                                                    int k, double* sc, double* scal, int32_t* st,
+                                                    int32_t* flags, double rtol) {
+  const int c = blockIdx.x;
+  if (*col_done(st, c)) return;
+  const double t = col_total(partial + (int64_t)c * nb, nb, threadIdx.x);
+  if (threadIdx.x == 0) {
+    double* s = sc + 8 * c;
+    s[4] = t;
+    *col_iters(st, c) += 1;
+    atomicAdd(flags + 2, 1);
+    if (t <= rtol * rtol * s[3]) {
+      finish_col(st, c, k);
+      record_rel(scal, sqrt(t / s[3]));
+    } else if (!(t >= 0.0)) {
+      breakdown_col(st, c, k, flags);  // NaN residual
+    }
+  }
+}
+
+// k_pcg_p per column: rho = r.z, beta = rho / rho_old (first: 0), p = z + beta p
+__global__ __launch_bounds__(kPcgThreads) void k_pcgmv_p(const double* __restrict__ Z,
+                                                         double* __restrict__ P, int64_t n, int k,
+                                                         const double* __restrict__ rz,
+                                                         double* sc, int32_t* st, int32_t* flags,
+                                                         int first, int it) {
+  __shared__ double tot[kPcgCT];
+  __shared__ double be[kPcgCT];
+  const int c0 = blockIdx.y * kPcgCT;
+  unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  if (!live) return;
+  tile_totals(rz, gridDim.x, c0, live, tot);
+  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
+    const int c = threadIdx.x;
+    double* s = sc + 8 * (c0 + c);
+    const double t = tot[c];
+    const double beta = first ? 0.0 : t / s[6 + (it & 1)];
+    be[c] = beta;
+    if (blockIdx.x == 0) {
+      if (!(t > 0.0)) {  // r.z <= 0 or NaN: the preconditioner is not positive definite
+        breakdown_col(st, c0 + c, k, flags);
+      } else {
+        s[6 + ((it + 1) & 1)] = t;
+        s[0] = t;
+        s[2] = beta;
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c)
+    if (((live >> c) & 1u) && !(tot[c] > 0.0)) live &= ~(1u << c);
+  if (!live) return;
+  double beta[kPcgCT];
+#pragma unroll
+  for (int c = 0; c < kPcgCT; ++c) beta[c] = ((live >> c) & 1u) ? be[c] : 0.0;
+  for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kPcgThreads) {
+    const double* z = Z + i * (int64_t)k + c0;
+    double* p = P + i * (int64_t)k + c0;
+#pragma unroll
+    for (int c = 0; c < kPcgCT; ++c)
+      if ((live >> c) & 1u) p[c] = z[c] + beta[c] * p[c];
+  }
+}
+
+// k_pcg_end per column (thread c): a column that did not reach the tolerance is counted; the
+// single solve's "iterations of the last solve" becomes the last column's
+__global__ __launch_bounds__(64) void k_pcgmv_end(int k, const double* sc, double* scal,
+                                                  int32_t* st, int32_t* flags) {
+  const int c = threadIdx.x;
+  if (c < k && !*col_done(st, c)) {
+    atomicAdd(flags + 1, 1);
+    record_rel(scal, sqrt(sc[8 * c + 4] / sc[8 * c + 3]));
+    *col_done(st, c) = 1;
+  }
+  if (c == k - 1) {
+    flags[0] = *col_iters(st, c);
+    st[0] = 1;
+    st[1] = k;
+  }
+}
+
+// the solver's n x k work blocks (leading dimension k), partials, per-column scalars and state
+static int pcg_mv_workspace(mlamg_pcg* C, int k, hipStream_t s) {
+  const size_t blk =
+      ((sizeof(double) * (size_t)std::max<int64_t>(C->n, 1) * (size_t)std::max(k, C->mv_kcap)) +
+       255) & ~size_t(255);
+  const size_t part = 2 * sizeof(double) * (size_t)MLAMG_MV_MAX * kPcgMaxBlocks;
+  const size_t scal = sizeof(double) * 8 * MLAMG_MV_MAX;
+  const size_t state = (sizeof(int32_t) * (8 + 2 * MLAMG_MV_MAX) + 255) & ~size_t(255);
+  if (k > C->mv_kcap) {
+    if (C->mv_mem) (void)hipFree(C->mv_mem);  // ordered after every earlier use (cache semantics)
+    C->mv_mem = nullptr;
+    C->mv_kcap = 0;
+    const size_t total = 3 * blk + part + scal + state;
+    MLAMG_HIP(hipMalloc(&C->mv_mem, total));
+    // p is read (times beta = 0) before it is first written: no NaN may lie there
+    MLAMG_HIP(hipMemsetAsync(C->mv_mem, 0, total, s));
+    C->mv_kcap = k;
+    char* p = static_cast<char*>(C->mv_mem);
+    C->R = reinterpret_cast<double*>(p);
+    C->P = reinterpret_cast<double*>(p + blk);
+    C->Q = reinterpret_cast<double*>(p + 2 * blk);
+    C->mv_partial = reinterpret_cast<double*>(p + 3 * blk);
+    C->mv_scal = reinterpret_cast<double*>(p + 3 * blk + part);
+    C->mv_state = reinterpret_cast<int32_t*>(p + 3 * blk + part + scal);
+  }
+  return MLAMG_OK;
+}
+
+static int pcg_iteration_mv(mlamg_pcg* C, double* X, int64_t ldx, int k, int it, hipStream_t s) {
+  const int nb = C->nb;
+  const int64_t n = C->n;
+  const dim3 g(nb, (k + kPcgCT - 1) / kPcgCT), t(kPcgThreads);
+  double* pa = C->mv_partial;                                       // p.q, then r.z partials
+  double* pb = C->mv_partial + (size_t)MLAMG_MV_MAX * kPcgMaxBlocks;  // r.r partials
+  int32_t* st = C->mv_state;
+  MLAMG_TRY(spmm_set_mv(C->A, C->P, k, C->Q, k, k, 1.0, 0.0, s, st));
+  hipLaunchKernelGGL(k_pcgmv_dot, g, t, 0, s, C->P, C->Q, n, k, pa, st);
+  hipLaunchKernelGGL(k_pcgmv_update, g, t, 0, s, X, ldx, C->R, C->P, C->Q, n, k, C->mv_scal, pa,
+                     pb, st, C->flags, it);
+  hipLaunchKernelGGL(k_pcgmv_check, dim3(k), dim3(64), 0, s, pb, nb, k, C->mv_scal, C->scal, st,
+                     C->flags, C->rtol);
+  double* Z = nullptr;
+  MLAMG_TRY(hier_coarse_cycle_mv(C->M, C->R, &Z, k, s, st));
+  hipLaunchKernelGGL(k_pcgmv_dot, g, t, 0, s, C->R, Z, n, k, pa, st);
+  hipLaunchKernelGGL(k_pcgmv_p, g, t, 0, s, Z, C->P, n, k, pa, C->mv_scal, st, C->flags, 0, it);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int pcg_solve_mv_impl(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                      hipStream_t s) {
+  if (C->n == 0) return MLAMG_OK;
+  MLAMG_TRY(hier_prepare_ext(C->M));
+  MLAMG_TRY(pcg_mv_workspace(C, k, s));
+  const int nb = C->nb;
+  const int64_t n = C->n;
+  const dim3 g(nb, (k + kPcgCT - 1) / kPcgCT), t(kPcgThreads);
+  int32_t* st = C->mv_state;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  MLAMG_HIP(hipStreamIsCapturing(s, &cap));
+  const bool poll = cap == hipStreamCaptureStatusNone && C->done_host;
+  hipLaunchKernelGGL(k_pcgmv_init, g, t, 0, s, B, ldb, X, ldx, C->R, n, k, C->mv_partial, st,
+                     C->flags);
+  hipLaunchKernelGGL(k_pcgmv_bnorm, dim3(k), dim3(64), 0, s, C->mv_partial, nb, k, C->mv_scal, st);
+  double* Z = nullptr;
+  MLAMG_TRY(hier_coarse_cycle_mv(C->M, C->R, &Z, k, s, st));
+  // rho_0 = r.z into scal[6] of every column (iteration 0 reads it), p = z
+  hipLaunchKernelGGL(k_pcgmv_dot, g, t, 0, s, C->R, Z, n, k, C->mv_partial, st);
+  hipLaunchKernelGGL(k_pcgmv_p, g, t, 0, s, Z, C->P, n, k, C->mv_partial, C->mv_scal, st,
+                     C->flags, 1, -1);
+  // the all-done flag is polled exactly as pcg_solve_impl polls `done`
+  int grp = 0;
+  for (int it = 0; it < C->maxit; ++it) {
+    MLAMG_TRY(pcg_iteration_mv(C, X, ldx, k, it, s));
+    if (poll && (it + 1) % C->poll == 0 && it + 1 < C->maxit) {
+      const int slot = grp & 1;
+      MLAMG_HIP(hipMemcpyAsync(C->done_host + slot, st, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+      MLAMG_HIP(hipEventRecord(C->ev[slot], s));
+      if (grp > 0) {
+        MLAMG_HIP(hipEventSynchronize(C->ev[slot ^ 1]));
+        if (C->done_host[slot ^ 1]) break;
+      }
+      ++grp;
+    }
+  }
+  hipLaunchKernelGGL(k_pcgmv_end, dim3(1), dim3(64), 0, s, k, C->mv_scal, C->scal, st, C->flags);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
 int64_t pcg_rows(const mlamg_pcg* C) { return C->n; }
 mlamg_hier* pcg_inner(mlamg_pcg* C) { return C->M; }
 
@@ -402,6 +820,7 @@ int mlamg_pcg_create(const mlamg_csr* A, mlamg_hier* M, double rtol, int maxit,
 int mlamg_pcg_destroy(mlamg_pcg* C) {
   if (C) {
     if (C->mem) (void)hipFree(C->mem);
+    if (C->mv_mem) (void)hipFree(C->mv_mem);
     if (C->done_host) (void)hipHostFree(C->done_host);
     for (hipEvent_t e : C->ev)
       if (e) (void)hipEventDestroy(e);
@@ -414,6 +833,34 @@ int mlamg_pcg_solve(mlamg_pcg* C, const double* b, double* x, void* stream) {
   MLAMG_REQUIRE(C && (C->n == 0 || (b && x)), "NULL argument");
   MLAMG_REQUIRE(b != x, "b and x must differ");
   return pcg_solve_impl(C, b, x, nullptr, S(stream));
+}
+
+int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
+                       void* stream) {
+  MLAMG_REQUIRE(C, "C is NULL");
+  MLAMG_REQUIRE(B, "B is NULL");
+  MLAMG_REQUIRE(X, "X is NULL");
+  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
+  MLAMG_REQUIRE(ldb >= k, "ldb < k");
+  MLAMG_REQUIRE(ldx >= k, "ldx < k");
+  MLAMG_REQUIRE(B != X, "B and X must differ");
+  return pcg_solve_mv_impl(C, B, ldb, X, ldx, k, S(stream));
+}
+
+int mlamg_pcg_iters_mv(const mlamg_pcg* C, int32_t* iters, int k, void* stream) {
+  MLAMG_REQUIRE(C, "C is NULL");
+  MLAMG_REQUIRE(iters, "iters is NULL");
+  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
+  int32_t st[8 + 2 * MLAMG_MV_MAX];
+  std::memset(st, 0, sizeof(st));
+  if (C->mv_state) {
+    hipStream_t s = S(stream);
+    MLAMG_HIP(hipMemcpyAsync(st, C->mv_state, sizeof(st), hipMemcpyDeviceToHost, s));
+    MLAMG_HIP(hipStreamSynchronize(s));
+  }
+  MLAMG_REQUIRE(k <= st[2], "k exceeds the columns of the last block solve");
+  for (int c = 0; c < k; ++c) iters[c] = st[9 + 2 * c];
+  return MLAMG_OK;
 }
 
 int mlamg_pcg_breakdowns(const mlamg_pcg* C, int32_t* breakdowns, void* stream) {

@@ -34,6 +34,7 @@ struct EpiMV {
   const double* dinv;   // JACOBI: one weight per row, shared by the columns
   double* Y;            // output (AXPBY with beta != 0 and ADD also read it)
   int64_t ldy;
+  const int32_t* done;  // nullable stop flag: raised, the launch does nothing
 };
 
 __device__ __forceinline__ int64_t xcd_block_mv(int64_t b, int64_t nb) {
@@ -121,6 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_spmm_stream(const int32_t* __restr
   __shared__ double sv[kBlockNnz];
   __shared__ int32_t sc[kBlockNnz];
   __shared__ int32_t rp[kBlockRows + 1];
+  if (ep.done && *ep.done) return;
   const int b = (int)xcd_block_mv(blockIdx.x, gridDim.x);
   const int tid = threadIdx.x;
   const int r0 = blk[b];
@@ -234,8 +236,9 @@ static int launch_spmm(const mlamg_csr* A, const double* X, int64_t ldx, int k, 
 }
 
 int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                double alpha, double beta, hipStream_t s) {
+                double alpha, double beta, hipStream_t s, const int32_t* done) {
   EpiMV ep{};
+  ep.done = done;
   ep.op = MV_AXPBY;
   ep.alpha = alpha;
   ep.beta = beta;
@@ -245,8 +248,9 @@ int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int
 }
 
 int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                hipStream_t s) {
+                hipStream_t s, const int32_t* done) {
   EpiMV ep{};
+  ep.done = done;
   ep.op = MV_ADD;
   ep.Y = Y;
   ep.ldy = ldy;
@@ -254,8 +258,9 @@ int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int
 }
 
 int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
-                double* R, int64_t ldr, int k, hipStream_t s) {
+                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done) {
   EpiMV ep{};
+  ep.done = done;
   ep.op = MV_RESID;
   ep.B = B;
   ep.ldb = ldb;
@@ -266,8 +271,9 @@ int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* 
 
 int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
                     const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
-                    hipStream_t s) {
+                    hipStream_t s, const int32_t* done) {
   EpiMV ep{};
+  ep.done = done;
   ep.op = MV_JACOBI;
   ep.B = B;
   ep.ldb = ldb;
@@ -285,9 +291,10 @@ int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int
 __global__ __launch_bounds__(256) void k_diag_mv(double* __restrict__ X, int64_t ldx,
                                                  const double* __restrict__ d,
                                                  const double* __restrict__ R, int64_t ldr,
-                                                 int64_t n, int k, int mode) {
+                                                 int64_t n, int k, int mode,
+                                                 const int32_t* __restrict__ done) {
   const int64_t w = blockIdx.x * 256ll + threadIdx.x;
-  if (w >= n * k) return;
+  if (w >= n * k || (done && *done)) return;
   const int64_t i = w / k;
   const int c = (int)(w - i * k);
   const double r = R[i * ldr + c];
@@ -299,10 +306,11 @@ __global__ __launch_bounds__(256) void k_diag_mv(double* __restrict__ X, int64_t
 }
 
 int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ldr, int64_t n,
-            int k, int mode, hipStream_t s) {
+            int k, int mode, hipStream_t s, const int32_t* done) {
   if (n == 0) return MLAMG_OK;
   const int64_t nb = (n * k + 255) / 256;
-  hipLaunchKernelGGL(k_diag_mv, dim3((unsigned)nb), dim3(256), 0, s, X, ldx, d, R, ldr, n, k, mode);
+  hipLaunchKernelGGL(k_diag_mv, dim3((unsigned)nb), dim3(256), 0, s, X, ldx, d, R, ldr, n, k, mode,
+                     done);
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;
 }
@@ -444,10 +452,11 @@ int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s) {
 template <int MODE>
 __global__ __launch_bounds__(256) void k_gemv_mv(const double* __restrict__ M, int64_t n,
                                                  const double* __restrict__ B, int64_t ldb,
-                                                 double* __restrict__ Xo, int64_t ldx, int k) {
+                                                 double* __restrict__ Xo, int64_t ldx, int k,
+                                                 const int32_t* __restrict__ done) {
   const int64_t row = blockIdx.x * 4ll + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= n) return;
+  if (row >= n || (done && *done)) return;
   const double* r = M + row * n;
   const int64_t j0 = MODE == 2 ? row : 0, j1 = MODE == 1 ? row + 1 : n;
   for (int c0 = 0; c0 < k; c0 += kMvCT) {
@@ -488,15 +497,17 @@ __global__ __launch_bounds__(256) void k_gemv_mv(const double* __restrict__ M, i
 
 // X = A_c^-1 B; ytmp: n x k scratch (leading dimension k) of method 2's intermediate X b
 int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X, int64_t ldx,
-                   int k, double* ytmp, hipStream_t s) {
+                   int k, double* ytmp, hipStream_t s, const int32_t* done) {
   if (D->n == 0) return MLAMG_OK;
   const dim3 g((unsigned)((D->n + 3) / 4));
   if (D->method == 2) {
     MLAMG_REQUIRE(ytmp, "scratch allocation failed");
-    hipLaunchKernelGGL(k_gemv_mv<1>, g, dim3(256), 0, s, D->inv, D->n, B, ldb, ytmp, (int64_t)k, k);
-    hipLaunchKernelGGL(k_gemv_mv<2>, g, dim3(256), 0, s, D->inv, D->n, ytmp, (int64_t)k, X, ldx, k);
+    hipLaunchKernelGGL(k_gemv_mv<1>, g, dim3(256), 0, s, D->inv, D->n, B, ldb, ytmp, (int64_t)k, k,
+                       done);
+    hipLaunchKernelGGL(k_gemv_mv<2>, g, dim3(256), 0, s, D->inv, D->n, ytmp, (int64_t)k, X, ldx, k,
+                       done);
   } else {
-    hipLaunchKernelGGL(k_gemv_mv<0>, g, dim3(256), 0, s, D->inv, D->n, B, ldb, X, ldx, k);
+    hipLaunchKernelGGL(k_gemv_mv<0>, g, dim3(256), 0, s, D->inv, D->n, B, ldb, X, ldx, k, done);
   }
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;

@@ -172,6 +172,8 @@ SIGNATURES = {
     "mlamg_pcg_solve": (c_int, [c_vp, c_vp, c_vp, c_vp]),
     "mlamg_pcg_stats": (c_int, [c_vp, P_i32, P_i32, P_i32, P_dbl, c_vp]),
     "mlamg_pcg_breakdowns": (c_int, [c_vp, P_i32, c_vp]),
+    "mlamg_pcg_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mlamg_pcg_iters_mv": (c_int, [c_vp, P_i32, c_int, c_vp]),
     "mlamg_gmres": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_int, c_int, c_int, P_int, P_int,
                             c_vp, c_int, c_vp]),
     "mlamg_csr_symmetric": (c_int, [c_vp, c_dbl, P_int, c_vp]),

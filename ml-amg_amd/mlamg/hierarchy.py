@@ -1060,8 +1060,11 @@ class Hierarchy:
         remove_mean subtracts each column's mean after every cycle's post-smoothing
         (ns/model/loss.py:89). Returns the (n_cycles, k) history (numpy) of ||b - A x||_2
         (norm='residual') or ||x||_2 (norm='x') per column, taken after the mean removal; None
-        with history=False. A fixed cycle count, run eagerly; weighted-Jacobi levels with a
-        dense coarse solve only (MlamgError EUNSUPPORTED otherwise)."""
+        with history=False. A fixed cycle count, run eagerly. Weighted-Jacobi levels with a
+        dense or a PCG coarse solve (the block PCG, mlamg_pcg_solve_mv: per column the bits and
+        the iteration count of the single solve; a breakdown raises CoarseSolveError as in
+        cycle()); a GMRES coarse solve, a Gauss-Seidel level, a factored prolongation or a
+        VECTOR-format operator is refused (MlamgError EUNSUPPORTED)."""
         from .sparse import mv_block
         if norm not in ("residual", "x"):
             raise ValueError(f"unknown norm {norm!r}")
@@ -1077,13 +1080,15 @@ class Hierarchy:
         self._solve_call("mlamg_hier_vcycle_mv", self.handle, ptr(B), ldb, ptr(X), ldx, k,
                          int(n_cycles), 0 if norm == "residual" else 1, int(bool(remove_mean)),
                          ptr(hist), stream_ptr())
+        self.check_coarse()
         if not history:
             return None
         return hist[: int(n_cycles)].cpu().numpy()
 
     def precondition(self, b):
         """One V-cycle from a zero guess: the action of the preconditioner on b (a vector, or
-        an (n, k) block of k <= 64 right-hand sides: one cycle on every column)."""
+        an (n, k) block of k <= 64 right-hand sides: one block cycle, column j bitwise
+        precondition(b[:, j]); cycle_multi's coarse solves and refusals)."""
         if getattr(b, "ndim", 1) == 2:
             bd = to_device_vec(b)
             xd = torch.zeros_like(bd)

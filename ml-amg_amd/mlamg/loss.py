@@ -8,7 +8,10 @@ history into per-column convergence factors convs = (errs[-1] / errs[-3]) ** (1/
 softmax-weighted loss softmax(convs) @ convs (loss.py:92-94).
 
 Here the cycles run through the block V-cycle of the library (Hierarchy.cycle_multi,
-mlamg_hier_vcycle_mv): every operator is streamed once for all k columns.
+mlamg_hier_vcycle_mv): every operator is streamed once for all k columns. The coarse system is
+solved by the dense inverse up to Hierarchy.TWO_LEVEL_DENSE_MAX rows and by the block PCG
+(mlamg_pcg_solve_mv, to a relative residual of 1e-12) above, where the reference factorises
+A_H with a sparse direct solver at any size (loss.py:79).
 
 Differences from the reference, all stated:
   * fp64 throughout. The reference holds x, A and P in fp32 and only solves the coarse system in
@@ -19,7 +22,11 @@ Differences from the reference, all stated:
   * differentiable with respect to P's stored values only (amg_loss_and_grad, and the torch
     autograd surface amg_loss_values): the adjoint two-level cycle below, not torch autograd
     through the kernels. A and the test vectors are constants; asking for their gradients raises
-    NotImplementedError.
+    NotImplementedError. With a PCG coarse solve the adjoint treats the solve as exact (implicit
+    differentiation: the PCG iteration itself is not differentiated), so the gradient carries an
+    error of order rtol * cond(A_H) = 1e-12 cond(A_H) relative to the dense-coarse gradient. A
+    GMRES coarse solve (an A_H that is not symmetric, beyond the dense solver's size) is not
+    differentiated: NotImplementedError.
   * neumann_solve_fix=True (the Lagrange-row coarse system, loss.py:11-30,66-67,76-82) is not
     implemented and raises NotImplementedError, forward and backward.
 
@@ -31,7 +38,8 @@ pattern:
   1. g += x4 diag(ebar[c] / errs[c])         (ebar is nonzero for the last and third-last cycle)
   2. g <- g - colmean(g)
   3. nu2 times: g <- g - A^T (D g)
-  4. lam = -A_H^-T (P^T g)
+  4. lam = -A_H^-T (P^T g)                   (dense inverse, or PCG: A_H passed the symmetry
+                                              test, so the forward's solver serves A_H^T too)
   5. g <- g + A^T (P lam)
   6. dP += sample_P[g e^T + (A x2) lam^T]    (two mlamg_sddmm launches on P's handle)
   7. nu1 times: g <- g - A^T (D g)
@@ -88,6 +96,9 @@ def amg_loss(P, A, test_vecs, tot_num_loop=5, no_prerelax=1, no_postrelax=1,
     P, A       scipy sparse, DeviceCSR or torch sparse: N_F x N_C prolongator, N_F x N_F system
     test_vecs  int k: np.random.seed(0) normal (N_F, k) vectors, column-normalised
                (loss.py:58-60); or an (N_F, k) array / tensor used as given. k <= 64.
+    Any coarse size: the dense inverse, or the block PCG above Hierarchy.TWO_LEVEL_DENSE_MAX
+    rows (a breakdown raises CoarseSolveError); a GMRES coarse solve raises MlamgError
+    (EUNSUPPORTED).
     Returns the loss (float); with return_factors=True, (loss, convs, errs) with errs the
     (tot_num_loop + 1, k) history of ||x_j||_2 after each cycle."""
     if neumann_solve_fix:
@@ -193,10 +204,11 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
         raise ValueError(f"test_vecs must be ({n}, k), got {tuple(X.shape)}")
     k, _ = mv_block(X, n, "test_vecs")
     H = Hierarchy.two_level(A, P, omega=2.0 / 3.0, nu_pre=nu1, nu_post=nu2)
-    if H.dense is None:
+    if H.dense is None and H.pcg is None:
         raise NotImplementedError(
-            f"amg_loss_and_grad: a coarse operator of {H.Ac.shape[0]} rows is beyond the dense "
-            "coarse solve (PCG / GMRES coarse solves are not differentiated)")
+            f"amg_loss_and_grad: the coarse operator of {H.Ac.shape[0]} rows is not symmetric "
+            "and beyond the dense coarse solve, so its coarse solve is GMRES, which is not "
+            "differentiated (dense and PCG coarse solves are)")
     L = H.levels[0]
     Ad, Pd, Rd, dinv = L.A, L.P, L.R, L.dinv
     nc = Pd.shape[1]
@@ -205,6 +217,13 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
 
     def block(rows, *lead):
         return torch.empty(lead + (rows, k), dtype=torch.float64, device=dev)
+
+    def coarse_solve(rhs, out):
+        # the forward's solver; PCG was chosen because A_H is symmetric, so it is A_H^-T too
+        if H.pcg is not None:
+            call("mlamg_pcg_solve_mv", H.pcg, ptr(rhs), k, ptr(out), k, k, s)
+        else:
+            call("mlamg_dense_solve_mv", H.dense, ptr(rhs), k, ptr(out), k, k, s)
 
     # ---- recorded forward: the block cycle's own steps (csrc/hier.hip mlamg_hier_vcycle_mv)
     ncyc = T + 1
@@ -219,7 +238,7 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
                  nu1, s)
         call("mlamg_residual_mv", Ad.handle, None, 0, ptr(X), k, ptr(r), k, k, None, s)
         call("mlamg_restrict_mv", Rd.handle, ptr(r), k, ptr(bc), k, k, s)
-        call("mlamg_dense_solve_mv", H.dense, ptr(bc), k, ptr(E[c]), k, k, s)
+        coarse_solve(bc, E[c])
         call("mlamg_prolong_add_mv", Pd.handle, ptr(E[c]), k, ptr(X), k, k, s)
         X2[c].copy_(X)
         if nu2:
@@ -230,6 +249,7 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
         if c in (T, T - 2):
             X4[c] = X.clone()
     errs = errs_d.cpu().numpy()
+    H.check_coarse()  # a PCG breakdown in the forward: CoarseSolveError
     loss, convs = loss_from_errs(errs)
 
     # ---- cotangents of the error history (host arithmetic on k numbers)
@@ -246,12 +266,18 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
     DA = DeviceCSR(h)
     M = DA.transpose()  # (D A)^T: one adjoint Jacobi sweep is g - M g
     del DA
+    HT = None
     if csr_symmetric(Ad, 0.0):
-        AT, dense_T, HT = Ad, H.dense, None
+        AT, solve_T = Ad, coarse_solve
     else:
         AT = Ad.transpose()
-        HT = Hierarchy.two_level(AT, Pd, omega=2.0 / 3.0, coarse="dense")  # A_c = A_H^T
-        dense_T = HT.dense
+        if H.pcg is not None:  # A_H symmetric to rounding though A is not exactly symmetric
+            solve_T = coarse_solve
+        else:
+            HT = Hierarchy.two_level(AT, Pd, omega=2.0 / 3.0, coarse="dense")  # A_c = A_H^T
+
+            def solve_T(rhs, out):
+                call("mlamg_dense_solve_mv", HT.dense, ptr(rhs), k, ptr(out), k, k, s)
 
     def adjoint_jacobi(g, g2, nu):
         for _ in range(nu):
@@ -271,7 +297,7 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
         call("mlamg_remove_mean_mv", ptr(g), k, n, k, s)
         g, g2 = adjoint_jacobi(g, g2, nu2)
         call("mlamg_restrict_mv", Rd.handle, ptr(g), k, ptr(t), k, k, s)
-        call("mlamg_dense_solve_mv", dense_T, ptr(t), k, ptr(lam), k, k, s)
+        solve_T(t, lam)
         lam.neg_()
         Pd.matmat(lam, out=q)
         AT.matmat(q, out=g, alpha=1.0, beta=1.0)
@@ -281,6 +307,7 @@ def _loss_and_grad_device(P, A, test_vecs, tot_num_loop, no_prerelax, no_postrel
         if c:  # the cotangent of the starting vectors is not asked for
             g, g2 = adjoint_jacobi(g, g2, nu1)
     torch.cuda.current_stream().synchronize()  # HT / M are released on return
+    H.check_coarse()  # a PCG breakdown in the backward solves
     return loss, dP, convs, errs
 
 
@@ -294,17 +321,24 @@ def amg_loss_and_grad(P, A, test_vecs, tot_num_loop=5, no_prerelax=1, no_postrel
     a coalesced torch COO P the order of P.values()). A P that is not canonical raises
     ValueError. The recorded forward runs the block cycle's own primitives step by step, so
     errs (and the loss) are bitwise amg_loss's. The backward pass is the adjoint cycle of the
-    module docstring: SpMM launches on A^T, (D A)^T, P and P^T, the dense coarse solve on
-    A_H^T (the forward's handle when A is exactly symmetric, else a second two-level setup on
-    A^T) and two mlamg_sddmm launches per cycle.
+    module docstring: SpMM launches on A^T, (D A)^T, P and P^T, the coarse solve on A_H^T and
+    two mlamg_sddmm launches per cycle. The coarse solve is the forward's: the dense inverse
+    (its handle when A is exactly symmetric, else a second two-level setup on A^T), or above
+    Hierarchy.TWO_LEVEL_DENSE_MAX rows the block PCG (mlamg_pcg_solve_mv), forward and backward
+    on the same solver, since PCG is only chosen for an A_H that passed the symmetry test. The
+    adjoint treats the PCG solve as exact (implicit differentiation), so against the
+    dense-coarse gradient the result differs by the order of rtol * cond(A_H) (rtol = 1e-12;
+    DESIGN.md §20 has the measured figures). A PCG breakdown in either pass raises
+    CoarseSolveError.
 
     Memory held between the forward and the backward pass: x2 and e of every cycle and x4 of
     two, (tot_num_loop + 1) (n + n_c) k + 2 n k doubles, plus five n x k and three n_c x k
     work blocks.
 
-    Refused: neumann_solve_fix=True (NotImplementedError), a coarse operator beyond the dense
-    coarse solve (NotImplementedError), k > 64 and tot_num_loop < 2 (ValueError), test_vecs or
-    A requiring grad (NotImplementedError)."""
+    Refused: neumann_solve_fix=True (NotImplementedError), a GMRES coarse solve (a coarse
+    operator that is not symmetric and beyond the dense solver's size: NotImplementedError),
+    k > 64 and tot_num_loop < 2 (ValueError), test_vecs or A requiring grad
+    (NotImplementedError)."""
     if neumann_solve_fix:
         raise NotImplementedError("amg_loss_and_grad: " + _NEUMANN_MSG)
     _refuse_grad_of(A, test_vecs, "amg_loss_and_grad")
@@ -356,7 +390,9 @@ def amg_loss_values(values, indptr, indices, shape, A, test_vecs, tot_num_loop=5
     backward returns grad_output * d loss / d values (amg_loss_and_grad's array, computed
     with the forward) and None for everything else; otherwise it is amg_loss's float. Only P's
     values are differentiable: a test_vecs tensor or a torch A that requires grad raises
-    NotImplementedError naming the argument. Not twice differentiable."""
+    NotImplementedError naming the argument. Dense and PCG coarse solves as in
+    amg_loss_and_grad; a GMRES coarse solve raises NotImplementedError. Not twice differentiable
+    (the backward is once_differentiable: a second derivative raises)."""
     import torch
     from .sparse import DeviceCSR, _device
     if neumann_solve_fix:
