@@ -390,6 +390,20 @@ int mlamg_gs_create_ex(const mlamg_csr* A, int sweep, int block, mlamg_gs** out,
 int mlamg_gs_destroy(mlamg_gs* G);
 int mlamg_gs_levels(const mlamg_gs* G, int32_t* n_levels);
 int mlamg_gs_sweep(const mlamg_gs* G, double* x, const double* b, int iterations, void* stream);
+/* The same sweeps on a block of k right-hand sides (multivectors as in the multi-vector section
+ * below: fp64, row-major n x k, ld >= k, 1 <= k <= MLAMG_MV_MAX, 8-byte-aligned pointers, odd ld
+ * allowed), X swept in place: the level schedule is walked once for all k columns. COLUMN j OF X
+ * IS BITWISE mlamg_gs_sweep ON COLUMN j, for every handle mlamg_gs_create / _create_ex makes
+ * (forward, backward, symmetric; gauss_seidel and block_gauss_seidel arithmetic): the smoother of
+ * the reference driver (ns/lib/multigrid.py:175,184) and of pyamg's smoothed-aggregation solver
+ * (ns/preconditioner/PyAMG.py:94) on a block. B may be NULL: every b_i is +0.0. B != X. NULL
+ * arguments, k out of range, ld < k and B == X return MLAMG_EINVAL before any device call. */
+int mlamg_gs_sweep_mv(const mlamg_gs* G, double* X, int64_t ldx, const double* B, int64_t ldb,
+                      int k, int iterations, void* stream);
+/* which kernels mlamg_gs_sweep_mv runs for k columns on G's (forward) schedule, a host function
+ * of (G, k): 0 = one launch per level, 1 = one-workgroup walk on the CSR arrays, 2 = one-workgroup
+ * walk on the level-ordered packed copy (csrc/gs_mv.hip) */
+int mlamg_gs_mv_path(const mlamg_gs* G, int k, int32_t* path);
 
 /* ---------------------------------------------------------------- coarse direct solve
  * Replaces spla.factorized/splu (multigrid.py:168; MLAMG.py:122): the coarse operator is
@@ -615,11 +629,21 @@ int mlamg_dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, dou
  * ||x||_2 (norm_mode 1), taken after the mean removal. A fixed cycle count (no tolerance stop),
  * run eagerly. The coarsest solve is the dense inverse (mlamg_dense_solve_mv) or the block PCG
  * (mlamg_pcg_solve_mv; a breakdown is counted in the solver's statistics, not returned).
- * MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother, a GMRES coarse solve, a factored
- * prolongation, or any operator in the VECTOR format. */
+ * MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother (unless the hierarchy asked for it:
+ * mlamg_hier_set_mv_gauss_seidel), a GMRES coarse solve, a factored prolongation, or any operator
+ * in the VECTOR format. */
 int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
                          int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
                          void* stream);
+/* on != 0: mlamg_hier_vcycle_mv takes Gauss-Seidel levels (mlamg_hier_set_level_smoother) through
+ * mlamg_gs_sweep_mv, mirroring the single cycle's steps (a coarse Gauss-Seidel level sweeps a
+ * zeroed iterate block in place; the finest sweeps X in place), so column j keeps the bits of
+ * mlamg_hier_vcycle on column j: the reference driver's amg_2_v smoother
+ * (ns/lib/multigrid.py:175,184) and pyamg's symmetric block Gauss-Seidel on every level
+ * (ns/preconditioner/PyAMG.py:94) on a block of right-hand sides. Jacobi and Gauss-Seidel levels
+ * may mix. Default 0: such a hierarchy is refused as before. A Krylov solver's inner hierarchy
+ * (mlamg_pcg_solve_mv) stays weighted-Jacobi only. */
+int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on);
 
 /* X = A^-1 B by PCG on the n_c x k block (B, X) (multivectors as above; B != X): the iteration
  * of mlamg_pcg_solve on every column at once, the operator and the preconditioner's hierarchy

@@ -378,6 +378,10 @@ int hier_prepare_ext(mlamg_hier* H);
 int gs_sweep_impl(const mlamg_gs* G, double* x, const double* b, int iterations,
                   const int32_t* done, hipStream_t s);
 int64_t gs_rows(const mlamg_gs* G);
+// the same sweeps on the n x k block (X in place, B nullable: +0.0), per column the bits of
+// gs_sweep_impl on that column (gs_mv.hip; arguments already validated)
+int gs_sweep_mv_impl(const mlamg_gs* G, double* X, int64_t ldx, const double* B, int64_t ldb,
+                     int k, int iterations, const int32_t* done, hipStream_t s);
 // ||x||_2 of one cycle into hist[*counter] (+ tolerance flag), like the residual-norm path
 int norm_hist_impl(const double* x, int64_t n, double* partial, double* hist, int32_t* counter,
                    int32_t* done, double tol, hipStream_t s);

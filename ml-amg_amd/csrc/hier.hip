@@ -90,6 +90,8 @@ struct mlamg_hier {
   // k-wide copies of the level vectors for mlamg_hier_vcycle_mv, grown on demand
   void* mv_mem = nullptr;
   size_t mv_bytes = 0;
+  // mlamg_hier_vcycle_mv takes Gauss-Seidel levels (mlamg_hier_set_mv_gauss_seidel)
+  bool mv_gs = false;
 };
 
 
@@ -361,8 +363,11 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
 // multi-vector kernels of spmm.hip. The fusions of the single path (first sweep written by the
 // restriction or the end-of-cycle residual kernel) are left out: they are the same roundings, so
 // column j keeps the bits of the single-vector cycle on column j. Work buffers are k-wide copies
-// of the level vectors with leading dimension k. The coarsest solve is the dense inverse or the
-// block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner hierarchy.
+// of the level vectors with leading dimension k. A Gauss-Seidel level (taken once the hierarchy
+// asked, mlamg_hier_set_mv_gauss_seidel) smooths its block in place with the block sweep of
+// gs_mv.hip, as the single path does with gs_sweep_impl. The coarsest solve is the dense inverse
+// or the block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner
+// hierarchy.
 namespace {
 struct MvLevel {
   double* x = nullptr;    // l > 0: iterate
@@ -386,14 +391,15 @@ static int mv_unsupported(const char* why, const char* who = "mlamg_hier_vcycle_
 }
 
 // what the block cycle cannot run (MLAMG_EUNSUPPORTED, the message names it); pcg_ok: a PCG
-// coarsest solve is taken (the block PCG), else the coarsest solve must be the dense inverse
-static int mv_refusals(const mlamg_hier* H, bool pcg_ok, const char* who) {
+// coarsest solve is taken (the block PCG), else the coarsest solve must be the dense inverse;
+// gs_ok: Gauss-Seidel levels are taken (the block sweep, gs_mv.hip)
+static int mv_refusals(const mlamg_hier* H, bool pcg_ok, bool gs_ok, const char* who) {
   if (H->pcg && !pcg_ok)
     return mv_unsupported("the coarse solve is PCG (dense coarse solves only)", who);
   if (H->gm_inner)
     return mv_unsupported("the coarse solve is GMRES (dense coarse solves only)", who);
   for (const Level& L : H->lv) {
-    if (L.gs)
+    if (L.gs && !gs_ok)
       return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)", who);
     if (L.fac_A) return mv_unsupported("a level uses a factored prolongation", who);
     if (L.A->vec_width || L.P->vec_width || L.R->vec_width)
@@ -442,6 +448,7 @@ static int mv_workspace(mlamg_hier* H, int k, MvWork* W, bool level0_x = false) 
 static int smooth_mv(const Level& L, const double* B, int64_t ldb, double*& cur, int64_t& lc,
                      double*& other, int64_t& lo, int nu, int k, hipStream_t s,
                      const int32_t* done = nullptr) {
+  if (L.gs) return gs_sweep_mv_impl(L.gs, cur, lc, B, ldb, k, nu, done, s);  // in place
   for (int i = 0; i < nu; ++i) {
     MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s, done));
     std::swap(cur, other);
@@ -473,7 +480,11 @@ static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, 
   double* other = M.tmp;
   int64_t lc = k, lo = k;
   const size_t bytes = sizeof(double) * (size_t)L.n * (size_t)k;
-  if (H->nu_pre > 0) {
+  if (H->nu_pre > 0 && L.gs) {
+    MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
+    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre, k, s, done));
+    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done));
+  } else if (H->nu_pre > 0) {
     MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s, done));
     MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s, done));
     MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done));
@@ -496,7 +507,7 @@ static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, 
 namespace mlamg {
 int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
                          const int32_t* done) {
-  MLAMG_TRY(mv_refusals(H, false, "block cycle of a Krylov solver's inner hierarchy"));
+  MLAMG_TRY(mv_refusals(H, false, false, "block cycle of a Krylov solver's inner hierarchy"));
   MLAMG_TRY(hier_prepare(H));
   MvWork W;
   MLAMG_TRY(mv_workspace(H, k, &W, true));
@@ -516,7 +527,7 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
   MLAMG_REQUIRE(B != X, "B and X must differ");
   MLAMG_REQUIRE(n_cycles >= 0, "n_cycles < 0");
   MLAMG_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode must be 0 (residual) or 1 (x)");
-  MLAMG_TRY(mv_refusals(H, true, "mlamg_hier_vcycle_mv"));
+  MLAMG_TRY(mv_refusals(H, true, H->mv_gs, "mlamg_hier_vcycle_mv"));
   MLAMG_TRY(hier_prepare(H));
   hipStream_t s = S(stream);
   MvWork W;
@@ -549,8 +560,13 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
     double* cur = X;
     double* other = M.tmp;
     int64_t lc = ldx, lo = k;
-    if (!have_r) MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
-    if (H->nu_pre > 0) {
+    // a Gauss-Seidel finest level sweeps X in place: its first sweep reads no residual
+    const bool gs_pre = L.gs && H->nu_pre > 0;
+    if (!have_r && !gs_pre) MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
+    if (gs_pre) {
+      MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre, k, s));
+      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s));
+    } else if (H->nu_pre > 0) {
       MLAMG_TRY(diag_mv(X, ldx, L.dinv, M.r, k, L.n, k, 0, s));
       MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre - 1, k, s));
       MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s));
@@ -582,6 +598,12 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
     }
   }
   MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on) {
+  MLAMG_REQUIRE(H, "H is NULL");
+  H->mv_gs = on != 0;
   return MLAMG_OK;
 }
 

@@ -153,6 +153,8 @@ SIGNATURES = {
     "mlamg_gs_destroy": (c_int, [c_vp]),
     "mlamg_gs_levels": (c_int, [c_vp, P_i32]),
     "mlamg_gs_sweep": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
+    "mlamg_gs_sweep_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
+    "mlamg_gs_mv_path": (c_int, [c_vp, c_int, P_i32]),
     "mlamg_dense_create": (c_int, [c_vp, c_vpp, c_vp]),
     "mlamg_dense_info": (c_int, [c_vp, P_int, P_i64]),
     "mlamg_dense_destroy": (c_int, [c_vp]),
@@ -182,6 +184,7 @@ SIGNATURES = {
     "mlamg_hier_set_factored_prolong": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp]),
     "mlamg_hier_set_level_smoother": (c_int, [c_vp, c_int, c_vp]),
     "mlamg_hier_set_norm": (c_int, [c_vp, c_int]),
+    "mlamg_hier_set_mv_gauss_seidel": (c_int, [c_vp, c_int]),
     "mlamg_hier_vcycle": (c_int, [c_vp, c_vp, c_vp, c_int, c_dbl, c_vp, P_i32, c_int, c_vp]),
     "mlamg_hier_cycle_bytes": (c_int, [c_vp, P_dbl]),
     "mlamg_hier_cycle_format_bytes": (c_int, [c_vp, P_dbl]),

@@ -1052,6 +1052,14 @@ class Hierarchy:
         k = min(1 if it == 0 else it + 1, cap)
         return x, {"info": info.value, "iters": it, "residuals": np.array(hist[:k])}
 
+    def enable_block_gauss_seidel(self, on=True):
+        """Let cycle_multi / precondition(B) take this hierarchy's Gauss-Seidel levels
+        (mlamg_hier_set_mv_gauss_seidel): each such level smooths the whole block with one block
+        sweep (mlamg_gs_sweep_mv), and column j keeps the bits of the single-vector cycle on
+        column j. Off by default, where a Gauss-Seidel level is refused. Returns self."""
+        call("mlamg_hier_set_mv_gauss_seidel", self.handle, int(bool(on)))
+        return self
+
     def cycle_multi(self, B, X, n_cycles, norm="residual", remove_mean=False, history=True):
         """Run n_cycles V-cycles in place on the block X of k <= 64 vectors (cuda fp64 (n, k)
         tensors with unit column stride; B=None: a zero right-hand side) through the
@@ -1063,8 +1071,10 @@ class Hierarchy:
         with history=False. A fixed cycle count, run eagerly. Weighted-Jacobi levels with a
         dense or a PCG coarse solve (the block PCG, mlamg_pcg_solve_mv: per column the bits and
         the iteration count of the single solve; a breakdown raises CoarseSolveError as in
-        cycle()); a GMRES coarse solve, a Gauss-Seidel level, a factored prolongation or a
-        VECTOR-format operator is refused (MlamgError EUNSUPPORTED)."""
+        cycle()). Gauss-Seidel levels (two_level(smoother="gauss_seidel"), pyamg_sa) are taken
+        after enable_block_gauss_seidel(), through the block sweep mlamg_gs_sweep_mv, and may mix
+        with Jacobi levels; without it such a level is refused, as are a GMRES coarse solve, a
+        factored prolongation and a VECTOR-format operator (MlamgError EUNSUPPORTED)."""
         from .sparse import mv_block
         if norm not in ("residual", "x"):
             raise ValueError(f"unknown norm {norm!r}")
@@ -1088,7 +1098,8 @@ class Hierarchy:
     def precondition(self, b):
         """One V-cycle from a zero guess: the action of the preconditioner on b (a vector, or
         an (n, k) block of k <= 64 right-hand sides: one block cycle, column j bitwise
-        precondition(b[:, j]); cycle_multi's coarse solves and refusals)."""
+        precondition(b[:, j]); cycle_multi's coarse solves and refusals: a hierarchy with
+        Gauss-Seidel levels, pyamg_sa's for one, needs enable_block_gauss_seidel() first)."""
         if getattr(b, "ndim", 1) == 2:
             bd = to_device_vec(b)
             xd = torch.zeros_like(bd)

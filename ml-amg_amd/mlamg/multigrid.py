@@ -96,8 +96,33 @@ class GaussSeidel:
         self.n_levels = int(n.value)
 
     def sweep(self, x, b, iterations=1):
+        """`iterations` sweeps in place on x. A 2-D x is a block of k <= 64 vectors (a cuda fp64
+        (n, k) tensor with unit column stride, b likewise or None for a zero right-hand side):
+        one mlamg_gs_sweep_mv, whose column j is bitwise the sweep of column j alone."""
+        if getattr(x, "ndim", 1) == 2:
+            from .sparse import mv_block
+            n = self.A.shape[0]
+            k, ldx = mv_block(x, n, "x")
+            ldb = 0
+            if b is not None:
+                kb, ldb = mv_block(b, n, "b")
+                if kb != k:
+                    raise ValueError(f"b has {kb} columns, x has {k}")
+            call("mlamg_gs_sweep_mv", self.handle, ptr(x), ldx, ptr(b), ldb, k, int(iterations),
+                 stream_ptr())
+            return x
         call("mlamg_gs_sweep", self.handle, ptr(x), ptr(b), int(iterations), stream_ptr())
         return x
+
+    def mv_path(self, k):
+        """The kernels a block sweep of k columns runs (mlamg_gs_mv_path): 0 = one launch per
+        level, 1 = one-workgroup walk on the CSR arrays, 2 = the walk on the packed copy."""
+        from .sparse import MV_MAX
+        if not 1 <= int(k) <= MV_MAX:
+            raise ValueError(f"k = {k}; the block path takes 1 to {MV_MAX} columns")
+        p = ctypes.c_int32()
+        call("mlamg_gs_mv_path", self.handle, int(k), ctypes.byref(p))
+        return int(p.value)
 
     def __del__(self):
         h = getattr(self, "handle", None)
