@@ -610,6 +610,28 @@ int mlamg_restrict_mv(const mlamg_csr* R, const double* Rf, int64_t ldr, double*
 int mlamg_prolong_add_mv(const mlamg_csr* P, const double* E, int64_t lde, double* X, int64_t ldx,
                          int k, void* stream);
 
+/* The same four products with every row summed in the CANONICAL CSR-VECTOR ORDER instead of
+ * scipy's (csrc/spmm_vec.hip; the order of the VECTOR format: 512 virtual lanes, entry e of a row
+ * to lane e mod 512, an xor butterfly per 64 lanes, the eight wave sums added in order; restated
+ * in oracle/oracle.c vec_matvec). COLUMN j OF EVERY RESULT IS BITWISE THE SINGLE-VECTOR ENTRY ON
+ * COLUMN j WITH THE VECTOR FORMAT ACTIVE ON THE HANDLE, AT ANY WIDTH: mlamg_spmv (alpha and beta
+ * as there; with beta == 0 Y is not read), mlamg_residual, mlamg_jacobi, mlamg_prolong_add; a
+ * restriction is mlamg_spmm_vec(R, ..., 1, 0). The result does not depend on the handle's vector
+ * width, on k, on leading dimensions or on pointer alignment. norms: as mlamg_residual_mv. The
+ * entries read the CSR arrays (the 16-bit column copy of the VECTOR format where the handle has
+ * one) and, like mlamg_spmm, do not require a particular active format: on a handle whose active
+ * format is VECTOR these, not mlamg_spmm and its kin, give the bits of the single-vector
+ * entries. Arguments and their checks as above; the message names the argument. */
+int mlamg_spmm_vec(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy,
+                   int k, double alpha, double beta, void* stream);
+int mlamg_residual_mv_vec(const mlamg_csr* A, const double* B, int64_t ldb, const double* X,
+                          int64_t ldx, double* R, int64_t ldr, int k, double* norms, void* stream);
+int mlamg_jacobi_mv_vec(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb,
+                        double* X, int64_t ldx, double* X_tmp, int64_t ldt, int k, int nu,
+                        void* stream);
+int mlamg_prolong_add_mv_vec(const mlamg_csr* P, const double* E, int64_t lde, double* X,
+                             int64_t ldx, int k, void* stream);
+
 /* out[j] (DEVICE, k doubles) = ||X[:, j]||_2, bitwise mlamg_norm2 of that column. */
 int mlamg_norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, void* stream);
 
@@ -631,7 +653,7 @@ int mlamg_dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, dou
  * (mlamg_pcg_solve_mv; a breakdown is counted in the solver's statistics, not returned).
  * MLAMG_EUNSUPPORTED for a Gauss-Seidel level smoother (unless the hierarchy asked for it:
  * mlamg_hier_set_mv_gauss_seidel), a GMRES coarse solve, a factored prolongation, or any operator
- * in the VECTOR format. */
+ * in the VECTOR format (unless the hierarchy asked for it: mlamg_hier_set_mv_vector). */
 int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
                          int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
                          void* stream);
@@ -644,6 +666,14 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
  * may mix. Default 0: such a hierarchy is refused as before. A Krylov solver's inner hierarchy
  * (mlamg_pcg_solve_mv) stays weighted-Jacobi only. */
 int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on);
+/* on != 0: mlamg_hier_vcycle_mv takes operators in the VECTOR format (which the family rule of
+ * mlamg_hier_apply_formats gives every long-row coarse operator). Each launch of the block cycle
+ * then follows its own operator: the canonical-order kernel (mlamg_spmm_vec and its kin) for an
+ * operator whose format is VECTOR, the scipy-order kernel for every other one, so column j keeps
+ * the bits of mlamg_hier_vcycle on column j. Formats may mix within a level; composes with
+ * mlamg_hier_set_mv_gauss_seidel and with a PCG coarse solve. Default 0: such a hierarchy is
+ * refused as before. A Krylov solver's inner hierarchy (mlamg_pcg_solve_mv) keeps refusing. */
+int mlamg_hier_set_mv_vector(mlamg_hier* H, int on);
 
 /* X = A^-1 B by PCG on the n_c x k block (B, X) (multivectors as above; B != X): the iteration
  * of mlamg_pcg_solve on every column at once, the operator and the preconditioner's hierarchy
@@ -658,7 +688,10 @@ int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on);
  * mlamg_pcg_breakdowns) afterwards read as after k single solves, column 0 first. The n_c x k
  * work blocks are owned by the solver and grown on demand (not capture-safe on first use of a
  * larger k). MLAMG_EUNSUPPORTED where the preconditioner's hierarchy has no block cycle (see
- * mlamg_hier_vcycle_mv; its coarsest solve must be dense). Not reentrant on one solver. */
+ * mlamg_hier_vcycle_mv; its coarsest solve must be dense). Not reentrant on one solver. The
+ * solver's own A p product is summed in scipy's order whatever A's format: on an A in the VECTOR
+ * format the columns are not the bits of mlamg_pcg_solve (hierarchies set up through
+ * mlamg/hierarchy.py never put a PCG operator there). */
 int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
                        void* stream);
 /* iters[j] (HOST, k entries) = iterations column j took in the last mlamg_pcg_solve_mv (k at

@@ -390,16 +390,20 @@ int count_out_of_range(const int32_t* a, int64_t n, int64_t lo, int64_t hi, hipS
 // multi-vector (row-major n x k, leading dimension ld) building blocks of the block V-cycle
 // (spmm.hip); per column the bits of the single-vector functions above. done (nullable): a
 // device flag; once it is raised the launch does nothing (the block PCG's all-columns-done flag,
-// the single path's stop flag on a block)
+// the single path's stop flag on a block). canon: every row is summed in the canonical CSR-vector
+// order (k_spmm_vcan, spmm_vec.hip: per column the bits of the single path with the VECTOR format
+// active) instead of scipy's
 int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                double alpha, double beta, hipStream_t s, const int32_t* done = nullptr);
+                double alpha, double beta, hipStream_t s, const int32_t* done = nullptr,
+                bool canon = false);
 int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                hipStream_t s, const int32_t* done = nullptr);
+                hipStream_t s, const int32_t* done = nullptr, bool canon = false);
 int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
-                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done = nullptr);
+                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done = nullptr,
+                bool canon = false);
 int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
                     const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
-                    hipStream_t s, const int32_t* done = nullptr);
+                    hipStream_t s, const int32_t* done = nullptr, bool canon = false);
 // mode 0: X += d .* R (jacobi_from_residual), mode 1: X = d .* R (jacobi_from_zero)
 int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ldr, int64_t n,
             int k, int mode, hipStream_t s, const int32_t* done = nullptr);

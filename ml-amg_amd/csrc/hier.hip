@@ -92,6 +92,8 @@ struct mlamg_hier {
   size_t mv_bytes = 0;
   // mlamg_hier_vcycle_mv takes Gauss-Seidel levels (mlamg_hier_set_mv_gauss_seidel)
   bool mv_gs = false;
+  // mlamg_hier_vcycle_mv takes VECTOR-format operators (mlamg_hier_set_mv_vector)
+  bool mv_vec = false;
 };
 
 
@@ -367,7 +369,9 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
 // asked, mlamg_hier_set_mv_gauss_seidel) smooths its block in place with the block sweep of
 // gs_mv.hip, as the single path does with gs_sweep_impl. The coarsest solve is the dense inverse
 // or the block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner
-// hierarchy.
+// hierarchy. An operator in the VECTOR format (taken once the hierarchy asked,
+// mlamg_hier_set_mv_vector) goes through the canonical-order kernel of spmm_vec.hip, every other
+// one through k_spmm_stream: each launch follows its own operator's format, as the single path's.
 namespace {
 struct MvLevel {
   double* x = nullptr;    // l > 0: iterate
@@ -385,6 +389,10 @@ struct MvWork {
   const int32_t* done = nullptr;  // stop flag of every launch (hier_coarse_cycle_mv's caller's)
 };
 
+// the operator's rows are summed in the canonical CSR-vector order (it is in the VECTOR format;
+// mv_refusals has let it pass)
+static inline bool canon(const mlamg_csr* A) { return A->vec_width != 0; }
+
 static int mv_unsupported(const char* why, const char* who = "mlamg_hier_vcycle_mv") {
   set_error(std::string(who) + ": " + why);
   return MLAMG_EUNSUPPORTED;
@@ -392,8 +400,10 @@ static int mv_unsupported(const char* why, const char* who = "mlamg_hier_vcycle_
 
 // what the block cycle cannot run (MLAMG_EUNSUPPORTED, the message names it); pcg_ok: a PCG
 // coarsest solve is taken (the block PCG), else the coarsest solve must be the dense inverse;
-// gs_ok: Gauss-Seidel levels are taken (the block sweep, gs_mv.hip)
-static int mv_refusals(const mlamg_hier* H, bool pcg_ok, bool gs_ok, const char* who) {
+// gs_ok: Gauss-Seidel levels are taken (the block sweep, gs_mv.hip); vec_ok: VECTOR-format
+// operators are taken (the canonical-order kernel, spmm_vec.hip)
+static int mv_refusals(const mlamg_hier* H, bool pcg_ok, bool gs_ok, bool vec_ok,
+                       const char* who) {
   if (H->pcg && !pcg_ok)
     return mv_unsupported("the coarse solve is PCG (dense coarse solves only)", who);
   if (H->gm_inner)
@@ -402,7 +412,7 @@ static int mv_refusals(const mlamg_hier* H, bool pcg_ok, bool gs_ok, const char*
     if (L.gs && !gs_ok)
       return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)", who);
     if (L.fac_A) return mv_unsupported("a level uses a factored prolongation", who);
-    if (L.A->vec_width || L.P->vec_width || L.R->vec_width)
+    if (!vec_ok && (L.A->vec_width || L.P->vec_width || L.R->vec_width))
       return mv_unsupported("an operator is in the VECTOR format, whose row order is not scipy's",
                             who);
   }
@@ -450,7 +460,7 @@ static int smooth_mv(const Level& L, const double* B, int64_t ldb, double*& cur,
                      const int32_t* done = nullptr) {
   if (L.gs) return gs_sweep_mv_impl(L.gs, cur, lc, B, ldb, k, nu, done, s);  // in place
   for (int i = 0; i < nu; ++i) {
-    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s, done));
+    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s, done, canon(L.A)));
     std::swap(cur, other);
     std::swap(lc, lo);
   }
@@ -483,20 +493,20 @@ static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, 
   if (H->nu_pre > 0 && L.gs) {
     MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
     MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre, k, s, done));
-    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done));
+    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done, canon(L.A)));
   } else if (H->nu_pre > 0) {
     MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s, done));
     MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s, done));
-    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done));
+    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done, canon(L.A)));
   } else {
     MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
     MLAMG_HIP(hipMemcpyAsync(M.r, B, bytes, hipMemcpyDeviceToDevice, s));
   }
   double* bn = (l + 1 < H->lv.size()) ? W.lv[l + 1].b : W.bc;
-  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, done));
+  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, done, canon(L.R)));
   double* xn = nullptr;
   MLAMG_TRY(cycle_coarse_mv(H, W, l + 1, bn, &xn, s));
-  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s, done));
+  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s, done, canon(L.P)));
   other = (cur == M.x) ? M.tmp : M.x;
   MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_post, k, s, done));
   *res = cur;
@@ -507,7 +517,8 @@ static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, 
 namespace mlamg {
 int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
                          const int32_t* done) {
-  MLAMG_TRY(mv_refusals(H, false, false, "block cycle of a Krylov solver's inner hierarchy"));
+  MLAMG_TRY(
+      mv_refusals(H, false, false, false, "block cycle of a Krylov solver's inner hierarchy"));
   MLAMG_TRY(hier_prepare(H));
   MvWork W;
   MLAMG_TRY(mv_workspace(H, k, &W, true));
@@ -527,7 +538,7 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
   MLAMG_REQUIRE(B != X, "B and X must differ");
   MLAMG_REQUIRE(n_cycles >= 0, "n_cycles < 0");
   MLAMG_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode must be 0 (residual) or 1 (x)");
-  MLAMG_TRY(mv_refusals(H, true, H->mv_gs, "mlamg_hier_vcycle_mv"));
+  MLAMG_TRY(mv_refusals(H, true, H->mv_gs, H->mv_vec, "mlamg_hier_vcycle_mv"));
   MLAMG_TRY(hier_prepare(H));
   hipStream_t s = S(stream);
   MvWork W;
@@ -562,20 +573,21 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
     int64_t lc = ldx, lo = k;
     // a Gauss-Seidel finest level sweeps X in place: its first sweep reads no residual
     const bool gs_pre = L.gs && H->nu_pre > 0;
-    if (!have_r && !gs_pre) MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
+    if (!have_r && !gs_pre)
+      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s, nullptr, canon(L.A)));
     if (gs_pre) {
       MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre, k, s));
-      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s));
+      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s, nullptr, canon(L.A)));
     } else if (H->nu_pre > 0) {
       MLAMG_TRY(diag_mv(X, ldx, L.dinv, M.r, k, L.n, k, 0, s));
       MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre - 1, k, s));
-      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s));
+      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s, nullptr, canon(L.A)));
     }
     double* bn = H->lv.size() > 1 ? W.lv[1].b : W.bc;
-    MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s));
+    MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, nullptr, canon(L.R)));
     double* xn = nullptr;
     MLAMG_TRY(cycle_coarse_mv(H, W, 1, bn, &xn, s));
-    MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, lc, k, s));
+    MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, lc, k, s, nullptr, canon(L.P)));
     if (cur == X) {
       other = M.tmp;
       lo = k;
@@ -590,7 +602,7 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
     if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, L.n, k, s));
     have_r = false;
     if (hist && norm_mode == 0) {
-      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s));
+      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s, nullptr, canon(L.A)));
       MLAMG_TRY(norm2_mv(M.r, k, L.n, k, hist + (int64_t)c * k, s));
       have_r = true;
     } else if (hist) {
@@ -604,6 +616,12 @@ int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X,
 int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on) {
   MLAMG_REQUIRE(H, "H is NULL");
   H->mv_gs = on != 0;
+  return MLAMG_OK;
+}
+
+int mlamg_hier_set_mv_vector(mlamg_hier* H, int on) {
+  MLAMG_REQUIRE(H, "H is NULL");
+  H->mv_vec = on != 0;
   return MLAMG_OK;
 }
 

@@ -17,99 +17,15 @@
 // aligned pointers and even leading dimensions (VEC); otherwise the same kernel runs with 8-byte
 // accesses.
 #include "common.hpp"
+#include "spmm_epi.hpp"
 
 #include <hip/hip_runtime.h>
 
 namespace mlamg {
 
-enum MvOp : int { MV_AXPBY = 0, MV_RESID = 1, MV_JACOBI = 2, MV_ADD = 3 };
-
-struct EpiMV {
-  int op;
-  double alpha, beta;   // AXPBY
-  const double* B;      // RESID / JACOBI right-hand side (NULL: +0.0)
-  int64_t ldb;
-  const double* Xin;    // JACOBI: old iterate (the SpMM operand itself)
-  int64_t ldxin;
-  const double* dinv;   // JACOBI: one weight per row, shared by the columns
-  double* Y;            // output (AXPBY with beta != 0 and ADD also read it)
-  int64_t ldy;
-  const int32_t* done;  // nullable stop flag: raised, the launch does nothing
-};
-
 __device__ __forceinline__ int64_t xcd_block_mv(int64_t b, int64_t nb) {
   const int64_t q = nb >> 3, r = nb & 7, g = b & 7, i = b >> 3;
   return (g < r ? g * (q + 1) : r * (q + 1) + (g - r) * q) + i;
-}
-
-// two adjacent columns at p (the second only when `two`)
-template <bool VEC>
-__device__ __forceinline__ void ld2(const double* __restrict__ p, bool two, double& a, double& b) {
-  if constexpr (VEC) {
-    if (two) {
-      const double2 t = *reinterpret_cast<const double2*>(p);
-      a = t.x;
-      b = t.y;
-    } else {
-      a = p[0];
-      b = 0.0;
-    }
-  } else {
-    a = p[0];
-    b = two ? p[1] : 0.0;
-  }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void st2(double* __restrict__ p, bool two, double a, double b) {
-  if constexpr (VEC) {
-    if (two) {
-      *reinterpret_cast<double2*>(p) = make_double2(a, b);
-    } else {
-      p[0] = a;
-    }
-  } else {
-    p[0] = a;
-    if (two) p[1] = b;
-  }
-}
-
-// the single-vector epilogues (spmv.hip epi_store) on the column pair (c, c + 1) of `row`
-template <bool VEC>
-__device__ __forceinline__ void epi_mv(int64_t row, int c, bool two, double s0, double s1,
-                                       const EpiMV& e) {
-  double* y = e.Y + row * e.ldy + c;
-  double o0, o1;
-  if (e.op == MV_AXPBY) {
-    if (e.beta == 0.0) {
-      o0 = (e.alpha == 1.0) ? s0 : e.alpha * s0;
-      o1 = (e.alpha == 1.0) ? s1 : e.alpha * s1;
-    } else {
-      double y0, y1;
-      ld2<VEC>(y, two, y0, y1);
-      o0 = e.alpha * s0 + e.beta * y0;
-      o1 = e.alpha * s1 + e.beta * y1;
-    }
-  } else if (e.op == MV_RESID) {
-    double b0 = 0.0, b1 = 0.0;  // B NULL: a zero right-hand side (+0.0: the same bits)
-    if (e.B) ld2<VEC>(e.B + row * e.ldb + c, two, b0, b1);
-    o0 = b0 - s0;
-    o1 = b1 - s1;
-  } else if (e.op == MV_JACOBI) {
-    double b0 = 0.0, b1 = 0.0, x0, x1;
-    if (e.B) ld2<VEC>(e.B + row * e.ldb + c, two, b0, b1);
-    ld2<VEC>(e.Xin + row * e.ldxin + c, two, x0, x1);
-    const double d = e.dinv[row];
-    const double r0 = b0 - s0, r1 = b1 - s1;
-    o0 = x0 + d * r0;
-    o1 = x1 + d * r1;
-  } else {  // MV_ADD
-    double y0, y1;
-    ld2<VEC>(y, two, y0, y1);
-    o0 = y0 + s0;
-    o1 = y1 + s1;
-  }
-  st2<VEC>(y, two, o0, o1);
 }
 
 template <bool VEC>
@@ -214,17 +130,14 @@ __global__ __launch_bounds__(kThreads) void k_spmm_stream(const int32_t* __restr
   }
 }
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// One SpMM launch with epilogue `ep` (pointers and leading dimensions already validated).
+// One SpMM launch with epilogue `ep` (pointers and leading dimensions already validated). canon:
+// rows summed in the canonical CSR-vector order (spmm_vec.hip) instead of scipy's.
 static int launch_spmm(const mlamg_csr* A, const double* X, int64_t ldx, int k, const EpiMV& ep,
-                       hipStream_t s) {
+                       hipStream_t s, bool canon) {
+  if (canon) return launch_spmm_vcan(A, X, ldx, k, ep, s);
   if (A->n_rows == 0 || A->n_blocks == 0) return MLAMG_OK;
   MLAMG_REQUIRE(A->blk != nullptr, "operator has no row-block table");
-  bool vec = al16(X) && !(ldx & 1) && al16(ep.Y) && !(ep.ldy & 1);
-  if (ep.B) vec = vec && al16(ep.B) && !(ep.ldb & 1);
-  if (ep.op == MV_JACOBI) vec = vec && al16(ep.Xin) && !(ep.ldxin & 1);
-  if (vec) {
+  if (mv_vec16(X, ldx, ep)) {
     MLAMG_LAUNCH((k_spmm_stream<true>), dim3(A->n_blocks), dim3(kThreads), 0, s, A->indptr,
                  A->indices, A->data, A->blk, X, ldx, k, ep);
   } else {
@@ -236,7 +149,7 @@ static int launch_spmm(const mlamg_csr* A, const double* X, int64_t ldx, int k, 
 }
 
 int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                double alpha, double beta, hipStream_t s, const int32_t* done) {
+                double alpha, double beta, hipStream_t s, const int32_t* done, bool canon) {
   EpiMV ep{};
   ep.done = done;
   ep.op = MV_AXPBY;
@@ -244,21 +157,21 @@ int spmm_set_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int
   ep.beta = beta;
   ep.Y = Y;
   ep.ldy = ldy;
-  return launch_spmm(A, X, ldx, k, ep, s);
+  return launch_spmm(A, X, ldx, k, ep, s, canon);
 }
 
 int spmm_add_mv(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy, int k,
-                hipStream_t s, const int32_t* done) {
+                hipStream_t s, const int32_t* done, bool canon) {
   EpiMV ep{};
   ep.done = done;
   ep.op = MV_ADD;
   ep.Y = Y;
   ep.ldy = ldy;
-  return launch_spmm(A, X, ldx, k, ep, s);
+  return launch_spmm(A, X, ldx, k, ep, s, canon);
 }
 
 int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
-                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done) {
+                double* R, int64_t ldr, int k, hipStream_t s, const int32_t* done, bool canon) {
   EpiMV ep{};
   ep.done = done;
   ep.op = MV_RESID;
@@ -266,12 +179,12 @@ int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* 
   ep.ldb = ldb;
   ep.Y = R;
   ep.ldy = ldr;
-  return launch_spmm(A, X, ldx, k, ep, s);
+  return launch_spmm(A, X, ldx, k, ep, s, canon);
 }
 
 int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
                     const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
-                    hipStream_t s, const int32_t* done) {
+                    hipStream_t s, const int32_t* done, bool canon) {
   EpiMV ep{};
   ep.done = done;
   ep.op = MV_JACOBI;
@@ -282,7 +195,7 @@ int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int
   ep.dinv = dinv;
   ep.Y = Xout;
   ep.ldy = ldxout;
-  return launch_spmm(A, Xin, ldxin, k, ep, s);
+  return launch_spmm(A, Xin, ldxin, k, ep, s, canon);
 }
 
 // ---------------------------------------------------------------- row-wise vector kernels

@@ -196,6 +196,14 @@ SIGNATURES = {
                                 c_vp]),
     "mlamg_restrict_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
     "mlamg_prolong_add_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    # the same in the canonical CSR-vector order (csrc/spmm_vec.hip)
+    "mlamg_spmm_vec": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp]),
+    "mlamg_residual_mv_vec": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_vp,
+                                      c_vp]),
+    "mlamg_jacobi_mv_vec": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int,
+                                    c_int, c_vp]),
+    "mlamg_prolong_add_mv_vec": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    "mlamg_hier_set_mv_vector": (c_int, [c_vp, c_int]),
     "mlamg_norm2_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mlamg_remove_mean_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp]),
     "mlamg_dense_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),

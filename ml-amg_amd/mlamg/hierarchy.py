@@ -1060,6 +1060,17 @@ class Hierarchy:
         call("mlamg_hier_set_mv_gauss_seidel", self.handle, int(bool(on)))
         return self
 
+    def enable_block_vector(self, on=True):
+        """Let cycle_multi / precondition(B) take this hierarchy's operators in the 'vector'
+        format (mlamg_hier_set_mv_vector), where build()'s default coarse_format='auto' puts
+        every long-row coarse operator: each launch of the block cycle then follows its own
+        operator's format — the canonical-order kernel (mlamg_spmm_vec and its kin) for a
+        'vector' operator, the scipy-order one for the rest — and column j keeps the bits of the
+        single-vector cycle on column j. Off by default, where such an operator is refused.
+        Returns self."""
+        call("mlamg_hier_set_mv_vector", self.handle, int(bool(on)))
+        return self
+
     def cycle_multi(self, B, X, n_cycles, norm="residual", remove_mean=False, history=True):
         """Run n_cycles V-cycles in place on the block X of k <= 64 vectors (cuda fp64 (n, k)
         tensors with unit column stride; B=None: a zero right-hand side) through the
@@ -1073,8 +1084,11 @@ class Hierarchy:
         the iteration count of the single solve; a breakdown raises CoarseSolveError as in
         cycle()). Gauss-Seidel levels (two_level(smoother="gauss_seidel"), pyamg_sa) are taken
         after enable_block_gauss_seidel(), through the block sweep mlamg_gs_sweep_mv, and may mix
-        with Jacobi levels; without it such a level is refused, as are a GMRES coarse solve, a
-        factored prolongation and a VECTOR-format operator (MlamgError EUNSUPPORTED)."""
+        with Jacobi levels. Operators in the 'vector' format (build()'s coarse_format='auto'
+        puts the long-row coarse operators there) are taken after enable_block_vector(), through
+        the canonical-order kernel mlamg_spmm_vec, and may mix with the other formats. Without
+        the respective switch such a level or operator is refused, as are a GMRES coarse solve
+        and a factored prolongation (MlamgError EUNSUPPORTED)."""
         from .sparse import mv_block
         if norm not in ("residual", "x"):
             raise ValueError(f"unknown norm {norm!r}")
@@ -1099,7 +1113,9 @@ class Hierarchy:
         """One V-cycle from a zero guess: the action of the preconditioner on b (a vector, or
         an (n, k) block of k <= 64 right-hand sides: one block cycle, column j bitwise
         precondition(b[:, j]); cycle_multi's coarse solves and refusals: a hierarchy with
-        Gauss-Seidel levels, pyamg_sa's for one, needs enable_block_gauss_seidel() first)."""
+        Gauss-Seidel levels, pyamg_sa's for one, needs enable_block_gauss_seidel() first, one
+        with 'vector'-format operators, build()'s default on long-row coarse levels,
+        enable_block_vector())."""
         if getattr(b, "ndim", 1) == 2:
             bd = to_device_vec(b)
             xd = torch.zeros_like(bd)

@@ -167,18 +167,29 @@ class DeviceCSR:
         call("mlamg_spmv", self.handle, ptr(x), ptr(out), alpha, beta, stream_ptr())
         return out
 
-    def matmat(self, X, out=None, alpha=1.0, beta=0.0):
-        """out = alpha * A @ X + beta * out on a block of k <= MV_MAX vectors (mlamg_spmm): X
-        is a cuda fp64 (n_cols, k) tensor with unit column stride — contiguous, or a column
-        slice of a wider tensor, used in place. Column j is bitwise matvec(X[:, j])."""
+    def matmat(self, X, out=None, alpha=1.0, beta=0.0, order="csr"):
+        """out = alpha * A @ X + beta * out on a block of k <= MV_MAX vectors: X is a cuda fp64
+        (n_cols, k) tensor with unit column stride — contiguous, or a column slice of a wider
+        tensor, used in place. order names the summation order of a row:
+          'csr'     scipy's, left to right (mlamg_spmm): column j is bitwise matvec(X[:, j])
+                    while the active format is any but 'vector', and scipy's A @ X always;
+          'vector'  the canonical CSR-vector order (mlamg_spmm_vec): column j is bitwise
+                    matvec(X[:, j]) while the active format is 'vector', at any width;
+          'active'  'vector' if get_format()[0] == 'vector', else 'csr': column j is bitwise
+                    matvec(X[:, j]) whatever the format.
+        A @ X is matmat(X), i.e. 'csr'."""
+        if order not in ("csr", "vector", "active"):
+            raise ValueError(f"unknown order {order!r} (csr, vector or active)")
+        if order == "active":
+            order = "vector" if self.get_format()[0] == "vector" else "csr"
         k, ldx = mv_block(X, self.shape[1], "X")
         if out is None:
             out = torch.zeros((self.shape[0], k), dtype=torch.float64, device=X.device)
         ko, ldy = mv_block(out, self.shape[0], "out")
         if ko != k:
             raise ValueError(f"out has {ko} columns, X has {k}")
-        call("mlamg_spmm", self.handle, ptr(X), ldx, ptr(out), ldy, k, float(alpha), float(beta),
-             stream_ptr())
+        call("mlamg_spmm_vec" if order == "vector" else "mlamg_spmm", self.handle, ptr(X), ldx,
+             ptr(out), ldy, k, float(alpha), float(beta), stream_ptr())
         return out
 
     def sddmm(self, U, V, alpha=1.0, beta=0.0, out=None):
