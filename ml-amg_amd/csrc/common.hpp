@@ -39,7 +39,11 @@ const char* get_error();
     }                                                                                \
   } while (0)
 
-#define MLAMG_TRY(call)                                                              \
+// the width check of every C entry that takes an n x k block
+#define MLAMG_MV_K(k) \
+  MLAMG_REQUIRE((k) >= 1 && (k) <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]")
+
+#define MLAMG_TRY(call)                                                             \
   do {                                                                               \
     int _rc = (call);                                                                \
     if (_rc != MLAMG_OK) return _rc;                                                 \
@@ -313,7 +317,8 @@ int launch_spmv_plain(const mlamg_csr* A, const double* x, double* y, hipStream_
 int exclusive_scan_i64(const int64_t* in, int64_t* out, int64_t n, hipStream_t s);  // out[n] = total
 int exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, hipStream_t s);
 // entries of a[0..n) outside [lo, hi) (device check before any kernel indexes with them); syncs
-// V-cycle building blocks (spmv.hip, vec.hip, dense.hip, hier.hip), shared by the executors
+// V-cycle building blocks (spmv.hip, vec.hip, dense.hip, hier.hip, hier_mv.hip), shared by the
+// executors
 int residual_impl(const mlamg_csr* A, const double* b, const double* x, double* r, double* norm2,
                   double* hist, int32_t* counter, int32_t* done, double tol, double* copy_to,
                   const double* copy_from, double* partial, hipStream_t s,
@@ -362,11 +367,11 @@ mlamg_hier* pcg_inner(mlamg_pcg* C);
 // column (arguments already validated)
 int pcg_solve_mv_impl(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int64_t ldx, int k,
                       hipStream_t s);
-// hier_coarse_cycle on a block: one zero-guess cycle of H with its level 0 as a coarse level on
-// the n x k block B (leading dimension k); *X_out (leading dimension k) lies in H's block
-// workspace. done (nullable): a device flag that turns every launch of the cycle into a no-op
-// once it is raised. MLAMG_EUNSUPPORTED where mlamg_hier_vcycle_mv refuses, and for a coarsest
-// solve that is not dense.
+// hier_coarse_cycle on a block (hier_mv.hip): one zero-guess cycle of H with its level 0 as a
+// coarse level on the n x k block B (leading dimension k); *X_out (leading dimension k) lies in
+// H's block workspace. done (nullable): a device flag that turns every launch of the cycle into a
+// no-op once it is raised. MLAMG_EUNSUPPORTED where mlamg_hier_vcycle_mv refuses, and for a
+// coarsest solve that is not dense.
 int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
                          const int32_t* done = nullptr);
 // restarted left-preconditioned GMRES (scipy's algorithm) with one V-cycle of M as

@@ -1,5 +1,6 @@
-// What the two V-cycle executors (hier.hip, dhier.hip) share on the host side: the cache of one
-// captured cycle and the batched launch loop with its pinned copy of the stop flag.
+// What the V-cycle executors (hier.hip, dhier.hip) share on the host side: the cache of one
+// captured cycle and the batched launch loop with its pinned copy of the stop flag. (The block
+// executor hier_mv.hip launches eagerly; it gets this header with the handle, hier.hpp.)
 #pragma once
 #include "common.hpp"
 

@@ -13,93 +13,23 @@
 // x = Dinv_w b (0 + d*(b - A@0) bit for bit). The tolerance test runs on the device: the norm
 // kernel raises a flag and every later kernel of the call returns immediately, so a whole batch
 // of cycles is launched (or replayed from one captured hipGraph) without host round trips.
-#include "cycle.hpp"
+//
+// This unit is the single-vector executor, the hierarchy's setters and the byte model; the block
+// (n x k) cycle on the same handle is hier_mv.hip, and hier.hpp is what the two share.
 #include "formats.hpp"
+#include "hier.hpp"
 
 #include <hip/hip_runtime.h>
 
-namespace {
-struct Level {
-  const mlamg_csr* A = nullptr;
-  const double* dinv = nullptr;
-  const mlamg_csr* P = nullptr;
-  const mlamg_csr* R = nullptr;
-  int64_t n = 0;
-  double* x = nullptr;    // l > 0: iterate
-  double* b = nullptr;    // l > 0: right-hand side
-  double* r = nullptr;    // residual
-  double* tmp = nullptr;  // ping-pong partner of x
-  const mlamg_gs* gs = nullptr;  // Gauss-Seidel smoother (in place) instead of weighted Jacobi
-  // factored prolongation (opt-in, mlamg_hier_set_factored_prolong): x += t - (w D^-1) A t with
-  // t = Agg e, through fac_A (this level's A in the uniform row-pair format), instead of x += P e
-  const mlamg_csr* fac_A = nullptr;
-  const int32_t* fac_agg = nullptr;
-  const double* fac_dinv = nullptr;
-};
+using namespace mlamg;
 
 static int prolong_add(const Level& L, const double* e, double* x, const int32_t* done,
                        hipStream_t s) {
-  if (L.fac_A) return mlamg::spmv_fadd(L.fac_A, L.fac_agg, e, x, L.fac_dinv, done, s);
-  return mlamg::spmv_add(L.P, e, x, done, s);
+  if (L.fac_A) return spmv_fadd(L.fac_A, L.fac_agg, e, x, L.fac_dinv, done, s);
+  return spmv_add(L.P, e, x, done, s);
 }
-}  // namespace
 
-struct mlamg_hier {
-  std::vector<Level> lv;
-  const mlamg_csr* Ac = nullptr;
-  const mlamg_dense* D = nullptr;
-  mlamg_pcg* pcg = nullptr;  // coarse solve by inner-hierarchy PCG instead of a dense inverse
-  // coarse solve by GMRES preconditioned by one V-cycle of an inner hierarchy of A_c (a coarse
-  // operator that is not SPD and beyond the dense inverse's size: the reference's SuperLU
-  // factors any nonsingular A_H, ns/lib/multigrid.py:165-170)
-  mlamg_hier* gm_inner = nullptr;
-  double gm_rtol = 1e-14, gm_fail_rtol = 1e-10;
-  int gm_restart = 50, gm_maxiter = 20;
-  int32_t gm_solves = 0, gm_last_iters = 0, gm_total_iters = 0, gm_not_converged = 0;
-  double gm_worst_rel = 0.0;
-  double* xc = nullptr;
-  double* bc = nullptr;
-  int nu_pre = 1, nu_post = 1;
-  int norm_mode = 0;  // per-cycle history: 0 = ||b - A x||_2, 1 = ||x||_2 (amg_2_v error_tol)
-  void* mem = nullptr;
-  size_t mem_bytes = 0;
-  double* partial = nullptr;
-  int32_t* flags = nullptr;  // [0] counter, [1] done
-  bool ready = false;
-  // captured single cycle (mlamg_hier_vcycle), and captured zero-guess cycle with level 0 as a
-  // coarse level (hier_coarse_cycle: a Krylov preconditioner, or the distributed executor's
-  // replicated levels). Each is re-keyed on its own; a setter that changes the cycle drops both
-  mlamg::CycleGraph top_graph, coarse_graph;
-  void invalidate_graphs() {
-    top_graph.invalidate();
-    coarse_graph.invalidate();
-  }
-  mlamg::DoneHost done_host;  // pinned copy of flags[1], polled between batches of cycles
-  // the stop flag the cycle's kernels test: flags + 1, or nullptr while a no-tolerance
-  // mlamg_hier_vcycle runs (nothing can raise it, and every kernel would otherwise start with a
-  // dependent load of it). done_check = 1 keeps it on every launch (A/B, mlamg_hier_set_done_check)
-  int32_t* cur_done = nullptr;
-  int done_check = 0;
-  // a Krylov solver's workspace (gmres.hip), kept across calls and grown on demand: at C4 a
-  // restart-100 GMRES needs 101 fine vectors (8 GB), too large for the allocation cache
-  void* ws = nullptr;
-  size_t ws_bytes = 0;
-  // zero right-hand side for the paths that read b as a vector (Gauss-Seidel, coarse-only)
-  double* zero_b = nullptr;
-  bool zero_rhs = false;  // the last mlamg_hier_vcycle had b = NULL (cycle_bytes prices that)
-  // k-wide copies of the level vectors for mlamg_hier_vcycle_mv, grown on demand
-  void* mv_mem = nullptr;
-  size_t mv_bytes = 0;
-  // mlamg_hier_vcycle_mv takes Gauss-Seidel levels (mlamg_hier_set_mv_gauss_seidel)
-  bool mv_gs = false;
-  // mlamg_hier_vcycle_mv takes VECTOR-format operators (mlamg_hier_set_mv_vector)
-  bool mv_vec = false;
-};
-
-
-using namespace mlamg;
-
-static int64_t coarse_rows(const mlamg_hier* H) {
+int64_t mlamg::coarse_rows(const mlamg_hier* H) {
   if (H->D) return H->D->n;
   if (H->gm_inner) return H->Ac->n_rows;
   return pcg_rows(H->pcg);
@@ -150,20 +80,6 @@ static int coarse_solve(mlamg_hier* H, const double* b, double* x, const int32_t
   return pcg_solve_impl(H->pcg, b, x, done, s);
 }
 
-// Hands out consecutive 256-byte-aligned blocks of doubles from `base`. With base = nullptr it
-// only measures, so one layout function, run first on nullptr and then on the allocation, both
-// sizes a work buffer and carves it: the two passes cannot get out of step.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  char* here() const { return base ? base + off : nullptr; }
-  double* take(int64_t n) {
-    double* q = reinterpret_cast<double*>(here());
-    off += (sizeof(double) * (size_t)std::max<int64_t>(n, 1) + 255) & ~size_t(255);
-    return q;
-  }
-};
-
 // the layout of H->mem: the level vectors, the coarse pair, the norm partials, then the flags
 // (counter, done) in a last 256-byte block; returns the bytes needed
 static size_t hier_layout(mlamg_hier* H, char* base) {
@@ -184,7 +100,7 @@ static size_t hier_layout(mlamg_hier* H, char* base) {
   return c.off + 256;
 }
 
-static int hier_prepare(mlamg_hier* H) {
+int mlamg::hier_prepare(mlamg_hier* H) {
   if (H->ready) return MLAMG_OK;
   MLAMG_REQUIRE(H->D != nullptr || H->pcg != nullptr || H->gm_inner != nullptr,
                 "coarse solver not set (mlamg_hier_set_coarse / _pcg / _gmres)");
@@ -360,270 +276,7 @@ int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_gr
 }
 }  // namespace mlamg
 
-// ---------------------------------------------------------------- block (n x k) cycle
-// The step sequence of cycle_top / cycle_coarse on a row-major block of k vectors, through the
-// multi-vector kernels of spmm.hip. The fusions of the single path (first sweep written by the
-// restriction or the end-of-cycle residual kernel) are left out: they are the same roundings, so
-// column j keeps the bits of the single-vector cycle on column j. Work buffers are k-wide copies
-// of the level vectors with leading dimension k. A Gauss-Seidel level (taken once the hierarchy
-// asked, mlamg_hier_set_mv_gauss_seidel) smooths its block in place with the block sweep of
-// gs_mv.hip, as the single path does with gs_sweep_impl. The coarsest solve is the dense inverse
-// or the block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner
-// hierarchy. An operator in the VECTOR format (taken once the hierarchy asked,
-// mlamg_hier_set_mv_vector) goes through the canonical-order kernel of spmm_vec.hip, every other
-// one through k_spmm_stream: each launch follows its own operator's format, as the single path's.
-namespace {
-struct MvLevel {
-  double* x = nullptr;    // l > 0: iterate
-  double* b = nullptr;    // l > 0: right-hand side
-  double* r = nullptr;    // residual
-  double* tmp = nullptr;  // ping-pong partner of x
-};
-struct MvWork {
-  std::vector<MvLevel> lv;
-  double* xc = nullptr;
-  double* bc = nullptr;
-  double* yc = nullptr;  // dense method 2: the intermediate X b
-  double* r0 = nullptr;  // coarse-only hierarchy: residual of the history
-  int k = 0;
-  const int32_t* done = nullptr;  // stop flag of every launch (hier_coarse_cycle_mv's caller's)
-};
-
-// the operator's rows are summed in the canonical CSR-vector order (it is in the VECTOR format;
-// mv_refusals has let it pass)
-static inline bool canon(const mlamg_csr* A) { return A->vec_width != 0; }
-
-static int mv_unsupported(const char* why, const char* who = "mlamg_hier_vcycle_mv") {
-  set_error(std::string(who) + ": " + why);
-  return MLAMG_EUNSUPPORTED;
-}
-
-// what the block cycle cannot run (MLAMG_EUNSUPPORTED, the message names it); pcg_ok: a PCG
-// coarsest solve is taken (the block PCG), else the coarsest solve must be the dense inverse;
-// gs_ok: Gauss-Seidel levels are taken (the block sweep, gs_mv.hip); vec_ok: VECTOR-format
-// operators are taken (the canonical-order kernel, spmm_vec.hip)
-static int mv_refusals(const mlamg_hier* H, bool pcg_ok, bool gs_ok, bool vec_ok,
-                       const char* who) {
-  if (H->pcg && !pcg_ok)
-    return mv_unsupported("the coarse solve is PCG (dense coarse solves only)", who);
-  if (H->gm_inner)
-    return mv_unsupported("the coarse solve is GMRES (dense coarse solves only)", who);
-  for (const Level& L : H->lv) {
-    if (L.gs && !gs_ok)
-      return mv_unsupported("a level uses a Gauss-Seidel smoother (weighted Jacobi only)", who);
-    if (L.fac_A) return mv_unsupported("a level uses a factored prolongation", who);
-    if (!vec_ok && (L.A->vec_width || L.P->vec_width || L.R->vec_width))
-      return mv_unsupported("an operator is in the VECTOR format, whose row order is not scipy's",
-                            who);
-  }
-  return MLAMG_OK;
-}
-
-// the layout of H->mv_mem: k-wide level blocks (level 0 iterates in the caller's X and reads the
-// caller's B; as a coarse level, hier_coarse_cycle_mv, it has an iterate of its own: level0_x),
-// then the coarse blocks; returns the bytes needed
-static size_t mv_layout(const mlamg_hier* H, int k, MvWork* W, char* base, bool level0_x) {
-  Carver c{base};
-  auto take = [&](int64_t n) { return c.take(std::max<int64_t>(n, 1) * k); };
-  const size_t nl = H->lv.size();
-  const int64_t nc = coarse_rows(H);
-  W->lv.resize(nl);
-  for (size_t l = 0; l < nl; ++l) {
-    if (l > 0 || level0_x) W->lv[l].x = take(H->lv[l].n);
-    if (l > 0) W->lv[l].b = take(H->lv[l].n);
-    W->lv[l].r = take(H->lv[l].n);
-    W->lv[l].tmp = take(H->lv[l].n);
-  }
-  W->xc = take(nc);
-  W->bc = take(nc);
-  W->yc = take(nc);
-  if (nl == 0) W->r0 = take(nc);
-  W->k = k;
-  return c.off;
-}
-
-static int mv_workspace(mlamg_hier* H, int k, MvWork* W, bool level0_x = false) {
-  const size_t total = mv_layout(H, k, W, nullptr, level0_x);
-  if (H->mv_bytes < total) {
-    if (H->mv_mem) (void)hipFree(H->mv_mem);  // ordered after every earlier use (cache semantics)
-    H->mv_mem = nullptr;
-    H->mv_bytes = 0;
-    MLAMG_HIP(hipMalloc(&H->mv_mem, total));
-    H->mv_bytes = total;
-  }
-  mv_layout(H, k, W, static_cast<char*>(H->mv_mem), level0_x);
-  return MLAMG_OK;
-}
-
-static int smooth_mv(const Level& L, const double* B, int64_t ldb, double*& cur, int64_t& lc,
-                     double*& other, int64_t& lo, int nu, int k, hipStream_t s,
-                     const int32_t* done = nullptr) {
-  if (L.gs) return gs_sweep_mv_impl(L.gs, cur, lc, B, ldb, k, nu, done, s);  // in place
-  for (int i = 0; i < nu; ++i) {
-    MLAMG_TRY(jacobi_sweep_mv(L.A, L.dinv, B, ldb, cur, lc, other, lo, k, s, done, canon(L.A)));
-    std::swap(cur, other);
-    std::swap(lc, lo);
-  }
-  return MLAMG_OK;
-}
-
-// the coarsest solve on a block: dense inverse, or the block PCG (pcg.hip) on H's PCG solver
-static int coarse_solve_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
-                           int k, double* ytmp, hipStream_t s, const int32_t* done) {
-  if (H->D) return dense_solve_mv(H->D, B, ldb, X, ldx, k, ytmp, s, done);
-  return pcg_solve_mv_impl(H->pcg, B, ldb, X, ldx, k, s);
-}
-
-// one V-cycle below the finest level from a zero guess (cycle_coarse); every block has ld = k
-static int cycle_coarse_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, double** res,
-                           hipStream_t s) {
-  const int k = W.k;
-  const int32_t* done = W.done;
-  if (l == H->lv.size()) {
-    MLAMG_TRY(coarse_solve_mv(H, B, k, W.xc, k, k, W.yc, s, done));
-    *res = W.xc;
-    return MLAMG_OK;
-  }
-  const Level& L = H->lv[l];
-  MvLevel& M = W.lv[l];
-  double* cur = M.x;
-  double* other = M.tmp;
-  int64_t lc = k, lo = k;
-  const size_t bytes = sizeof(double) * (size_t)L.n * (size_t)k;
-  if (H->nu_pre > 0 && L.gs) {
-    MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
-    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre, k, s, done));
-    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done, canon(L.A)));
-  } else if (H->nu_pre > 0) {
-    MLAMG_TRY(diag_mv(cur, k, L.dinv, B, k, L.n, k, 1, s, done));
-    MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_pre - 1, k, s, done));
-    MLAMG_TRY(residual_mv(L.A, B, k, cur, k, M.r, k, k, s, done, canon(L.A)));
-  } else {
-    MLAMG_HIP(hipMemsetAsync(cur, 0, bytes, s));
-    MLAMG_HIP(hipMemcpyAsync(M.r, B, bytes, hipMemcpyDeviceToDevice, s));
-  }
-  double* bn = (l + 1 < H->lv.size()) ? W.lv[l + 1].b : W.bc;
-  MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, done, canon(L.R)));
-  double* xn = nullptr;
-  MLAMG_TRY(cycle_coarse_mv(H, W, l + 1, bn, &xn, s));
-  MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, k, k, s, done, canon(L.P)));
-  other = (cur == M.x) ? M.tmp : M.x;
-  MLAMG_TRY(smooth_mv(L, B, k, cur, lc, other, lo, H->nu_post, k, s, done));
-  *res = cur;
-  return MLAMG_OK;
-}
-}  // namespace
-
-namespace mlamg {
-int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
-                         const int32_t* done) {
-  MLAMG_TRY(
-      mv_refusals(H, false, false, false, "block cycle of a Krylov solver's inner hierarchy"));
-  MLAMG_TRY(hier_prepare(H));
-  MvWork W;
-  MLAMG_TRY(mv_workspace(H, k, &W, true));
-  W.done = done;
-  return cycle_coarse_mv(H, W, 0, B, X_out, s);
-}
-}  // namespace mlamg
-
 extern "C" {
-
-int mlamg_hier_vcycle_mv(mlamg_hier* H, const double* B, int64_t ldb, double* X, int64_t ldx,
-                         int k, int n_cycles, int norm_mode, int remove_mean, double* hist,
-                         void* stream) {
-  MLAMG_REQUIRE(H && X, "NULL argument");
-  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
-  MLAMG_REQUIRE(ldx >= k && (!B || ldb >= k), "leading dimension < k");
-  MLAMG_REQUIRE(B != X, "B and X must differ");
-  MLAMG_REQUIRE(n_cycles >= 0, "n_cycles < 0");
-  MLAMG_REQUIRE(norm_mode == 0 || norm_mode == 1, "norm_mode must be 0 (residual) or 1 (x)");
-  MLAMG_TRY(mv_refusals(H, true, H->mv_gs, H->mv_vec, "mlamg_hier_vcycle_mv"));
-  MLAMG_TRY(hier_prepare(H));
-  hipStream_t s = S(stream);
-  MvWork W;
-  MLAMG_TRY(mv_workspace(H, k, &W));
-  if (H->lv.empty()) {  // coarse-only hierarchy: X = A^-1 B each cycle
-    const int64_t nc = coarse_rows(H);
-    if (!B) {
-      MLAMG_HIP(hipMemsetAsync(W.bc, 0, sizeof(double) * (size_t)std::max<int64_t>(nc, 1) * k, s));
-      B = W.bc;
-      ldb = k;
-    }
-    if (hist && norm_mode == 0 && !H->Ac)
-      return mv_unsupported("a coarse-only hierarchy without its operator has no residual norm");
-    for (int c = 0; c < n_cycles; ++c) {
-      MLAMG_TRY(coarse_solve_mv(H, B, ldb, X, ldx, k, W.yc, s, nullptr));
-      if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, nc, k, s));
-      if (hist && norm_mode == 0) {
-        MLAMG_TRY(residual_mv(H->Ac, B, ldb, X, ldx, W.r0, k, k, s));
-        MLAMG_TRY(norm2_mv(W.r0, k, nc, k, hist + (int64_t)c * k, s));
-      } else if (hist) {
-        MLAMG_TRY(norm2_mv(X, ldx, nc, k, hist + (int64_t)c * k, s));
-      }
-    }
-    return MLAMG_OK;
-  }
-  const Level& L = H->lv[0];
-  MvLevel& M = W.lv[0];
-  bool have_r = false;  // M.r == B - A X (the end-of-cycle residual, reused by the next sweep)
-  for (int c = 0; c < n_cycles; ++c) {
-    double* cur = X;
-    double* other = M.tmp;
-    int64_t lc = ldx, lo = k;
-    // a Gauss-Seidel finest level sweeps X in place: its first sweep reads no residual
-    const bool gs_pre = L.gs && H->nu_pre > 0;
-    if (!have_r && !gs_pre)
-      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s, nullptr, canon(L.A)));
-    if (gs_pre) {
-      MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre, k, s));
-      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s, nullptr, canon(L.A)));
-    } else if (H->nu_pre > 0) {
-      MLAMG_TRY(diag_mv(X, ldx, L.dinv, M.r, k, L.n, k, 0, s));
-      MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_pre - 1, k, s));
-      MLAMG_TRY(residual_mv(L.A, B, ldb, cur, lc, M.r, k, k, s, nullptr, canon(L.A)));
-    }
-    double* bn = H->lv.size() > 1 ? W.lv[1].b : W.bc;
-    MLAMG_TRY(spmm_set_mv(L.R, M.r, k, bn, k, k, 1.0, 0.0, s, nullptr, canon(L.R)));
-    double* xn = nullptr;
-    MLAMG_TRY(cycle_coarse_mv(H, W, 1, bn, &xn, s));
-    MLAMG_TRY(spmm_add_mv(L.P, xn, k, cur, lc, k, s, nullptr, canon(L.P)));
-    if (cur == X) {
-      other = M.tmp;
-      lo = k;
-    } else {
-      other = X;
-      lo = ldx;
-    }
-    MLAMG_TRY(smooth_mv(L, B, ldb, cur, lc, other, lo, H->nu_post, k, s));
-    if (cur != X && L.n > 0)
-      MLAMG_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, cur, sizeof(double) * lc,
-                                 sizeof(double) * k, L.n, hipMemcpyDeviceToDevice, s));
-    if (remove_mean) MLAMG_TRY(remove_mean_mv(X, ldx, L.n, k, s));
-    have_r = false;
-    if (hist && norm_mode == 0) {
-      MLAMG_TRY(residual_mv(L.A, B, ldb, X, ldx, M.r, k, k, s, nullptr, canon(L.A)));
-      MLAMG_TRY(norm2_mv(M.r, k, L.n, k, hist + (int64_t)c * k, s));
-      have_r = true;
-    } else if (hist) {
-      MLAMG_TRY(norm2_mv(X, ldx, L.n, k, hist + (int64_t)c * k, s));
-    }
-  }
-  MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
-}
-
-int mlamg_hier_set_mv_gauss_seidel(mlamg_hier* H, int on) {
-  MLAMG_REQUIRE(H, "H is NULL");
-  H->mv_gs = on != 0;
-  return MLAMG_OK;
-}
-
-int mlamg_hier_set_mv_vector(mlamg_hier* H, int on) {
-  MLAMG_REQUIRE(H, "H is NULL");
-  H->mv_vec = on != 0;
-  return MLAMG_OK;
-}
 
 int mlamg_hier_create(mlamg_hier** out) {
   MLAMG_REQUIRE(out, "out is NULL");

@@ -840,7 +840,7 @@ int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, in
   MLAMG_REQUIRE(C, "C is NULL");
   MLAMG_REQUIRE(B, "B is NULL");
   MLAMG_REQUIRE(X, "X is NULL");
-  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
+  MLAMG_MV_K(k);
   MLAMG_REQUIRE(ldb >= k, "ldb < k");
   MLAMG_REQUIRE(ldx >= k, "ldx < k");
   MLAMG_REQUIRE(B != X, "B and X must differ");
@@ -850,7 +850,7 @@ int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, in
 int mlamg_pcg_iters_mv(const mlamg_pcg* C, int32_t* iters, int k, void* stream) {
   MLAMG_REQUIRE(C, "C is NULL");
   MLAMG_REQUIRE(iters, "iters is NULL");
-  MLAMG_REQUIRE(k >= 1 && k <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]");
+  MLAMG_MV_K(k);
   int32_t st[8 + 2 * MLAMG_MV_MAX];
   std::memset(st, 0, sizeof(st));
   if (C->mv_state) {

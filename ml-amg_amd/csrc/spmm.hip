@@ -426,12 +426,37 @@ int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X
   return MLAMG_OK;
 }
 
+// ---------------------------------------------------------------- bodies of the twin C entries
+// What mlamg_residual_mv / mlamg_jacobi_mv and their _vec twins (spmm_vec.hip) do once each has
+// checked its arguments; canon picks the summation order.
+int residual_mv_run(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                    double* R, int64_t ldr, int k, double* norms, hipStream_t s, bool canon) {
+  MLAMG_TRY(residual_mv(A, B, ldb, X, ldx, R, ldr, k, s, nullptr, canon));
+  if (norms) MLAMG_TRY(norm2_mv(R, ldr, A->n_rows, k, norms, s));
+  return MLAMG_OK;
+}
+
+// nu sweeps ping-ponging between X and X_tmp; the result is copied back when it ends in X_tmp
+int jacobi_mv_run(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb, double* X,
+                  int64_t ldx, double* X_tmp, int64_t ldt, int k, int nu, hipStream_t s,
+                  bool canon) {
+  double* cur = X;
+  double* nxt = X_tmp;
+  int64_t lc = ldx, ln = ldt;
+  for (int i = 0; i < nu; ++i) {
+    MLAMG_TRY(jacobi_sweep_mv(A, dinv_w, B, ldb, cur, lc, nxt, ln, k, s, nullptr, canon));
+    std::swap(cur, nxt);
+    std::swap(lc, ln);
+  }
+  if (cur != X && A->n_rows > 0)
+    MLAMG_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, cur, sizeof(double) * lc,
+                               sizeof(double) * k, A->n_rows, hipMemcpyDeviceToDevice, s));
+  return MLAMG_OK;
+}
+
 }  // namespace mlamg
 
 using namespace mlamg;
-
-#define MLAMG_MV_K(k) \
-  MLAMG_REQUIRE((k) >= 1 && (k) <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]")
 
 extern "C" {
 
@@ -451,9 +476,7 @@ int mlamg_residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const do
   MLAMG_REQUIRE(ldx >= k && ldr >= k && (!B || ldb >= k), "leading dimension < k");
   MLAMG_REQUIRE(A->n_rows == A->n_cols, "residual needs a square matrix");
   MLAMG_REQUIRE(X != R, "X and R must differ");
-  MLAMG_TRY(residual_mv(A, B, ldb, X, ldx, R, ldr, k, S(stream)));
-  if (norms) MLAMG_TRY(norm2_mv(R, ldr, A->n_rows, k, norms, S(stream)));
-  return MLAMG_OK;
+  return residual_mv_run(A, B, ldb, X, ldx, R, ldr, k, norms, S(stream), false);
 }
 
 int mlamg_jacobi_mv(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb,
@@ -465,19 +488,7 @@ int mlamg_jacobi_mv(const mlamg_csr* A, const double* dinv_w, const double* B, i
   MLAMG_REQUIRE(A->n_rows == A->n_cols, "jacobi needs a square matrix");
   MLAMG_REQUIRE(nu >= 0, "nu < 0");
   MLAMG_REQUIRE(X != X_tmp, "X_tmp must differ from X");
-  hipStream_t s = S(stream);
-  double* cur = X;
-  double* nxt = X_tmp;
-  int64_t lc = ldx, ln = ldt;
-  for (int i = 0; i < nu; ++i) {
-    MLAMG_TRY(jacobi_sweep_mv(A, dinv_w, B, ldb, cur, lc, nxt, ln, k, s));
-    std::swap(cur, nxt);
-    std::swap(lc, ln);
-  }
-  if (cur != X && A->n_rows > 0)
-    MLAMG_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, cur, sizeof(double) * lc,
-                               sizeof(double) * k, A->n_rows, hipMemcpyDeviceToDevice, s));
-  return MLAMG_OK;
+  return jacobi_mv_run(A, dinv_w, B, ldb, X, ldx, X_tmp, ldt, k, nu, S(stream), false);
 }
 
 int mlamg_restrict_mv(const mlamg_csr* R, const double* Rf, int64_t ldr, double* Bc, int64_t ldb,

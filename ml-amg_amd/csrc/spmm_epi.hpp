@@ -107,4 +107,13 @@ static inline bool mv_vec16(const double* X, int64_t ldx, const EpiMV& ep) {
 int launch_spmm_vcan(const mlamg_csr* A, const double* X, int64_t ldx, int k, const EpiMV& ep,
                      hipStream_t s);
 
+
+// what the C entries mlamg_residual_mv / mlamg_jacobi_mv and their _vec twins run after their own
+// argument checks (spmm.hip)
+int residual_mv_run(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                    double* R, int64_t ldr, int k, double* norms, hipStream_t s, bool canon);
+int jacobi_mv_run(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb, double* X,
+                  int64_t ldx, double* X_tmp, int64_t ldt, int k, int nu, hipStream_t s,
+                  bool canon);
+
 }  // namespace mlamg

@@ -248,9 +248,6 @@ int launch_spmm_vcan(const mlamg_csr* A, const double* X, int64_t ldx, int k, co
 
 using namespace mlamg;
 
-#define MLAMG_MV_K(k) \
-  MLAMG_REQUIRE((k) >= 1 && (k) <= MLAMG_MV_MAX, "k must be in [1, MLAMG_MV_MAX = 64]")
-
 extern "C" {
 
 int mlamg_spmm_vec(const mlamg_csr* A, const double* X, int64_t ldx, double* Y, int64_t ldy,
@@ -277,9 +274,7 @@ int mlamg_residual_mv_vec(const mlamg_csr* A, const double* B, int64_t ldb, cons
   MLAMG_REQUIRE(!B || ldb >= k, "ldb < k");
   MLAMG_REQUIRE(X != R, "X and R must differ");
   MLAMG_REQUIRE(A->n_rows == A->n_cols, "residual needs a square matrix");
-  MLAMG_TRY(residual_mv(A, B, ldb, X, ldx, R, ldr, k, S(stream), nullptr, true));
-  if (norms) MLAMG_TRY(norm2_mv(R, ldr, A->n_rows, k, norms, S(stream)));
-  return MLAMG_OK;
+  return residual_mv_run(A, B, ldb, X, ldx, R, ldr, k, norms, S(stream), true);
 }
 
 int mlamg_jacobi_mv_vec(const mlamg_csr* A, const double* dinv_w, const double* B, int64_t ldb,
@@ -296,19 +291,7 @@ int mlamg_jacobi_mv_vec(const mlamg_csr* A, const double* dinv_w, const double* 
   MLAMG_REQUIRE(nu >= 0, "nu < 0");
   MLAMG_REQUIRE(X != X_tmp, "X_tmp must differ from X");
   MLAMG_REQUIRE(A->n_rows == A->n_cols, "jacobi needs a square matrix");
-  hipStream_t s = S(stream);
-  double* cur = X;
-  double* nxt = X_tmp;
-  int64_t lc = ldx, ln = ldt;
-  for (int i = 0; i < nu; ++i) {
-    MLAMG_TRY(jacobi_sweep_mv(A, dinv_w, B, ldb, cur, lc, nxt, ln, k, s, nullptr, true));
-    std::swap(cur, nxt);
-    std::swap(lc, ln);
-  }
-  if (cur != X && A->n_rows > 0)
-    MLAMG_HIP(hipMemcpy2DAsync(X, sizeof(double) * ldx, cur, sizeof(double) * lc,
-                               sizeof(double) * k, A->n_rows, hipMemcpyDeviceToDevice, s));
-  return MLAMG_OK;
+  return jacobi_mv_run(A, dinv_w, B, ldb, X, ldx, X_tmp, ldt, k, nu, S(stream), true);
 }
 
 int mlamg_prolong_add_mv_vec(const mlamg_csr* P, const double* E, int64_t lde, double* X,

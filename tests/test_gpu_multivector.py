@@ -359,7 +359,7 @@ def hierarchies(ml, torch_cuda):
     return Hs
 
 
-@pytest.mark.parametrize("nu", ((1, 1), (2, 1), (0, 1)))
+@pytest.mark.parametrize("nu", ((1, 1), (2, 1), (0, 1), (1, 0), (2, 2), (0, 0)))
 @pytest.mark.parametrize("which", ("multilevel", "two_level"))
 def test_block_cycle_matches_single_cycles(ml, torch_cuda, hierarchies, which, nu):
     torch = torch_cuda
