@@ -41,6 +41,7 @@ extern "C" {
 
 typedef struct mlamg_csr mlamg_csr;
 typedef struct mlamg_dense mlamg_dense;
+typedef struct mlamg_blockdense mlamg_blockdense;
 typedef struct mlamg_hier mlamg_hier;
 typedef struct mlamg_gs mlamg_gs;
 typedef struct mlamg_pcg mlamg_pcg;
@@ -642,6 +643,48 @@ int mlamg_remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, void* stream)
  * dense operator is read once for all k columns. Not reentrant on one handle (method 2). */
 int mlamg_dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X,
                          int64_t ldx, int k, void* stream);
+
+/* ---- a batch of independent problems as one block-diagonal stack (mlamg/loss.py AmgLossBatch)
+ * The rows of a stacked multivector are cut into nb consecutive segments, segment s the rows
+ * [seg_offsets[s], seg_offsets[s + 1]) (DEVICE, nb + 1 int64 entries, ascending from 0); max_len
+ * is the longest segment's length (a shorter value gives unspecified results, never an access
+ * outside the segments). 1 <= nb <= 65535. All segments run in one launch per stage. NULL
+ * arguments, k out of range, ld < k and nb out of range return MLAMG_EINVAL before any device
+ * call; the message names the function and the argument. */
+
+/* out[s * k + j] (DEVICE, nb x k doubles) = ||X[segment s, j]||_2. FOR EVERY SEGMENT BITWISE
+ * mlamg_norm2_mv ON THAT SEGMENT'S ROWS ALONE: segment s keeps the single kernels' partition
+ * (min(1024, ceil(n_s / 256)) row blocks walked with the same stride, partials summed in the same
+ * order). */
+int mlamg_norm2_seg_mv(const double* X, int64_t ldx, int k, const int64_t* seg_offsets,
+                       int64_t nb, int64_t max_len, double* out, void* stream);
+
+/* every segment's rows lose their own column means. FOR EVERY SEGMENT BITWISE
+ * mlamg_remove_mean_mv ON THAT SEGMENT'S ROWS ALONE (the fixed 512 row blocks, the same order of
+ * the partials, the mean divides by n_s; row blocks that own no rows contribute the +0.0 they
+ * contribute there). */
+int mlamg_remove_mean_seg_mv(double* X, int64_t ldx, int k, const int64_t* seg_offsets,
+                             int64_t nb, int64_t max_len, void* stream);
+
+/* The inverses of the nb diagonal blocks of the square CSR A_c, block b the rows and columns
+ * [offsets_host[b], offsets_host[b + 1]) (HOST, nb + 1 entries from 0 to n). BLOCK b's INVERSE IS
+ * BITWISE WHAT mlamg_dense_create BUILDS FOR THAT BLOCK ALONE, by the same rule per block: 64
+ * rows or more try the inverse Cholesky factor first (method 1), smaller blocks and blocks that
+ * fail its symmetry or pivot test take Gauss-Jordan with partial pivoting (method 0); the whole
+ * batch is inverted in a handful of launches whatever nb is (csrc/blockdense.hip). MLAMG_EINVAL,
+ * with a message naming the row / the block: an entry outside the diagonal blocks (the first
+ * such row), a block at or above mlamg_dense_create's method-2 threshold (2048 rows; the batch
+ * is for small coarse problems), an exactly singular block. Syncs. */
+int mlamg_blockdense_create(const mlamg_csr* A_c, const int64_t* offsets_host, int64_t nb,
+                            mlamg_blockdense** out, void* stream);
+int mlamg_blockdense_destroy(mlamg_blockdense* D);
+/* nb, the stacked rows n and methods[b] (HOST, nb ints) = mlamg_dense_info's method of block b;
+ * every output is nullable */
+int mlamg_blockdense_info(const mlamg_blockdense* D, int64_t* nb, int64_t* n, int* methods);
+/* X_b = inv_b B_b for every block in one launch (B, X: stacked n x k multivectors). EVERY BLOCK'S
+ * ROWS ARE BITWISE mlamg_dense_solve_mv OF A HANDLE CREATED ON THAT BLOCK ALONE. B != X. */
+int mlamg_blockdense_solve_mv(const mlamg_blockdense* D, const double* B, int64_t ldb, double* X,
+                              int64_t ldx, int k, void* stream);
 
 /* n_cycles V(nu1,nu2) cycles of a finalised hierarchy on the block (B, X), X updated in place:
  * the step sequence of mlamg_hier_vcycle on every column, hence its bits. B may be NULL (zero

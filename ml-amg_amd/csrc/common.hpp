@@ -10,6 +10,7 @@
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -352,6 +353,12 @@ struct DenseJob {
   int64_t n;
 };
 int dense_chol_inverse_batch(const DenseJob* jobs, int count, bool* spd, hipStream_t s);
+// operators of at least this many rows keep the factor (mlamg_dense_info method 2) and are refused
+// by the block-diagonal inverse (blockdense.hip); MLAMG_DENSE_TRI_MIN overrides
+inline int64_t dense_tri_min() {
+  const char* e = std::getenv("MLAMG_DENSE_TRI_MIN");
+  return e ? std::atoll(e) : 2048;
+}
 int hier_coarse_cycle(mlamg_hier* H, const double* b, double** x_out, int use_graph,
                       hipStream_t s);
 int32_t* hier_done_flag(mlamg_hier* H);

@@ -603,12 +603,6 @@ using namespace mlamg;
 
 extern "C" {
 
-// operators of at least this many rows keep the factor (method 2); MLAMG_DENSE_TRI_MIN overrides
-static int64_t dense_tri_min() {
-  const char* e = std::getenv("MLAMG_DENSE_TRI_MIN");
-  return e ? std::atoll(e) : 2048;
-}
-
 int mlamg_dense_create(const mlamg_csr* A, mlamg_dense** out, void* stream) {
   MLAMG_REQUIRE(A && out, "NULL argument");
   MLAMG_REQUIRE(A->n_rows == A->n_cols, "square matrix required");

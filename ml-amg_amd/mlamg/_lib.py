@@ -207,6 +207,13 @@ SIGNATURES = {
     "mlamg_norm2_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "mlamg_remove_mean_mv": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp]),
     "mlamg_dense_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
+    # a batch of problems as one block-diagonal stack (csrc/seg_mv.hip, csrc/blockdense.hip)
+    "mlamg_norm2_seg_mv": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "mlamg_remove_mean_seg_mv": (c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_vp]),
+    "mlamg_blockdense_create": (c_int, [c_vp, c_vp, c_i64, c_vpp, c_vp]),
+    "mlamg_blockdense_destroy": (c_int, [c_vp]),
+    "mlamg_blockdense_info": (c_int, [c_vp, P_i64, P_i64, P_int]),
+    "mlamg_blockdense_solve_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_vp]),
     "mlamg_hier_vcycle_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_int,
                                      c_vp, c_vp]),
     "mlamg_sddmm": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_dbl, c_vp, c_vp]),
