@@ -236,36 +236,47 @@ int mlamg_evolution_strength(const mlamg_csr* A, double rho, double epsilon, int
 
 /* GNN inference layers of ns/model/agg_interp.py FullAggNet.forward (:432-486), fp32, device
  * pointers (csrc/gnn.hip). Graph = the CSR pattern of A (ns/model/data.py:22-46): edge e = stored
- * entry (src i, tgt j); tptr[n+1]/teid[E] list each target's incoming edges, ascending source.
- * Dense weights in torch Linear layout [out, in]; act 0 none, 1 relu; R (nullable) is added
- * after the activation, rc = its columns (1: broadcast). */
+ * entry (src i, tgt j); messages flow src -> tgt; tptr[n+1]/teid[E] list each target's incoming
+ * edges, ascending source. Dense weights in torch Linear layout [out, in]; act 0 none, 1 relu; R
+ * (nullable) is added after the activation, rc = its columns (1: broadcast). Every launch covers
+ * its whole index range whatever n, M or E (int32 edge ids: E < 2^31). A size outside the limit
+ * stated at a prototype returns MLAMG_EINVAL and writes nothing. */
+/* Y[M][N] = act(beta * Y + X[M][K] W[N][K]^T (+ b[N])) (+ R); beta == 0: Y is not read.
+ * Limits: 1 <= K <= 160, 1 <= N <= 64, M >= 0, rc in {1, N} when R is given. */
 int mlamg_gnn_linear(const float* X, int64_t M, int K, const float* W, const float* b, int N,
                      int act, float beta, const float* R, int rc, float* Y, void* stream);
-/* gcn_norm without self loops (TAGConv normalize=True): wn_e = deg^-1/2[src] w_e deg^-1/2[tgt] */
+/* gcn_norm without self loops (TAGConv normalize=True): deg_j = sum of w over edges with target
+ * j, dis_tmp[n] = deg^-1/2 (0 where deg == 0), wn_e = dis[src] w_e dis[tgt]. No size limit. */
 int mlamg_gnn_gcn_norm(const int32_t* tptr, const int32_t* teid, const int32_t* src,
                        const int32_t* tgt, const float* w, int64_t n, int64_t E, float* dis_tmp,
                        float* wn, void* stream);
-/* Y[i] = sum over incoming edges of w_e X[src_e] (TAGConv propagate, aggr 'add'), F <= 64 */
+/* Y[i] = sum over incoming edges of w_e X[src_e] (TAGConv propagate, aggr 'add'; a node without
+ * incoming edges gets 0). Limits: 1 <= F <= 64. */
 int mlamg_gnn_propagate(const int32_t* tptr, const int32_t* teid, const int32_t* src,
                         const float* w, const float* X, int64_t n, int F, float* Y, void* stream);
-/* torch_geometric InstanceNorm (affine False, no running stats): per channel over the nodes */
+/* torch_geometric InstanceNorm (affine False, no running stats): per channel over the nodes,
+ * (x - mean) / sqrt(biased variance + eps). Limits: n >= 1, F >= 1 (no upper limit). */
 int mlamg_gnn_instance_norm(const float* X, int64_t n, int F, float eps, float* Y, void* stream);
 /* NNConv(Fin, Fout, nn = Linear(fe,4)-ReLU-Linear(4,16)-ReLU-Linear(16,Fin*Fout)-ReLU), aggr
- * 'add', root weight `root` = X W_root^T (precomputed), bias; msg_tmp[E*Fout] scratch */
+ * 'add', root weight `root` = X W_root^T (precomputed), bias; msg_tmp[E*Fout] scratch (not
+ * touched when E == 0). Limits: 1 <= Fout <= 64, Fin >= 1, fe >= 1. */
 int mlamg_gnn_nnconv(const int32_t* tptr, const int32_t* teid, const int32_t* src,
                      const float* ea, int64_t E, int fe, const float* L1, const float* c1,
                      const float* L2, const float* c2, const float* L3, const float* c3,
                      const float* X, int64_t n, int Fin, int Fout, const float* root,
                      const float* bias, int act, const float* R, int rc, float* msg_tmp,
                      float* Y, void* stream);
-/* smallEdgeModel: Linear(2F+fe, H)-ReLU-LayerNorm(H)-Linear(H, C) on [x_src | x_tgt | ea] */
+/* smallEdgeModel: Linear(2F+fe, H)-ReLU-LayerNorm(H, eps 1e-5)-Linear(H, C) on
+ * [x_src | x_tgt | ea]; E == 0 returns without a launch.
+ * Limits: 1 <= H <= 64, 1 <= C <= 4, 2F + fe <= 160. */
 int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, int F,
                        const float* ea, int fe, int64_t E, const float* W1, const float* b1,
                        int H, const float* g, const float* beta, const float* W2,
                        const float* b2, int C, int act, const float* R, int rc, float* out,
                        void* stream);
-/* topk_vec (agg_interp.py:14-22): vec[n] = 1 at the k largest scores (ties: smaller index
- * first), idx[k] (nullable) = those nodes in that order. Syncs. */
+/* topk_vec (agg_interp.py:14-22): vec[n] = 1 at the k largest scores (ties, -0.0 == +0.0 among
+ * them: smaller index first), idx[k] (nullable) = those nodes in that order; the order of NaN
+ * scores is unspecified. Limits: 0 <= k <= n. Syncs. */
 int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_t* idx,
                    void* stream);
 

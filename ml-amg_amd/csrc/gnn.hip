@@ -28,6 +28,15 @@ __device__ __forceinline__ float wsumf(float v) {
   return v;
 }
 
+// Every kernel walks its items with this loop: block b takes items [b * per, (b + 1) * per),
+// this thread item `sub` of them, then the block strides on by the whole grid. blocks() below
+// sizes (and caps) the grid; the loop covers whatever the cap leaves, so no launch truncates
+// its index range. per and gridDim are block-uniform: where `sub` is too (a wave per item, a
+// block per tile) the whole wave / block leaves the loop together.
+#define MLAMG_GRID_STRIDE(i, n, per, sub)                                  \
+  for (int64_t i = (int64_t)blockIdx.x * (per) + (sub); i < (int64_t)(n); \
+       i += (int64_t)gridDim.x * (per))
+
 // Y[m][n] = beta * Y[m][n] + sum_k X[m][k] W[n][k] (+ b[n]) -> act -> (+ R[m][n or 0]).
 // A block stages W^T in LDS (K <= 160, N <= 64) and takes 256 / NP rows at a time, NP = N
 // rounded up to a power of two; lane n of a row reads W^T[k][n] (consecutive: no conflicts) and
@@ -44,7 +53,7 @@ __global__ void k_linear(const float* __restrict__ X, int64_t M, int K, const fl
   const int rows = kT / NP;
   const int r = threadIdx.x / NP, n = threadIdx.x % NP;
   if (n >= N) return;
-  for (int64_t m = (int64_t)blockIdx.x * rows + r; m < M; m += (int64_t)gridDim.x * rows) {
+  MLAMG_GRID_STRIDE(m, M, rows, r) {
     const float* x = X + m * K;
     float acc = 0.0f;
     for (int k = 0; k < K; ++k) acc = fmaf(x[k], wt[k * N + n], acc);
@@ -61,34 +70,33 @@ __global__ void k_linear(const float* __restrict__ X, int64_t M, int K, const fl
 __global__ void k_propagate(const int32_t* __restrict__ tptr, const int32_t* __restrict__ teid,
                             const int32_t* __restrict__ src, const float* __restrict__ w,
                             const float* __restrict__ X, int64_t n, int F, float* __restrict__ Y) {
-  const int64_t i = (int64_t)blockIdx.x * (kT / 64) + threadIdx.x / 64;
   const int f = threadIdx.x & 63;
-  if (i >= n || f >= F) return;
-  float acc = 0.0f;
-  for (int32_t q = tptr[i]; q < tptr[i + 1]; ++q) {
-    const int32_t e = teid[q];
-    acc = fmaf(w[e], X[(int64_t)src[e] * F + f], acc);
+  if (f >= F) return;
+  MLAMG_GRID_STRIDE(i, n, kT / 64, threadIdx.x / 64) {
+    float acc = 0.0f;
+    for (int32_t q = tptr[i]; q < tptr[i + 1]; ++q) {
+      const int32_t e = teid[q];
+      acc = fmaf(w[e], X[(int64_t)src[e] * F + f], acc);
+    }
+    Y[i * F + f] = acc;
   }
-  Y[i * F + f] = acc;
 }
 
 // gcn_norm without self loops (TAGConv normalize=True): deg_j = sum of w over edges with
 // target j; w'_e = deg^-1/2[src] w_e deg^-1/2[tgt] (inf -> 0)
 __global__ void k_deg_isqrt(const int32_t* __restrict__ tptr, const int32_t* __restrict__ teid,
                             const float* __restrict__ w, int64_t n, float* __restrict__ dis) {
-  const int64_t j = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (j >= n) return;
-  float d = 0.0f;
-  for (int32_t q = tptr[j]; q < tptr[j + 1]; ++q) d += w[teid[q]];
-  const float r = 1.0f / sqrtf(d);
-  dis[j] = isinf(r) ? 0.0f : r;
+  MLAMG_GRID_STRIDE(j, n, kT, threadIdx.x) {
+    float d = 0.0f;
+    for (int32_t q = tptr[j]; q < tptr[j + 1]; ++q) d += w[teid[q]];
+    const float r = 1.0f / sqrtf(d);
+    dis[j] = isinf(r) ? 0.0f : r;
+  }
 }
 __global__ void k_gcn_weight(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt,
                              const float* __restrict__ w, int64_t E, int wstride,
                              const float* __restrict__ dis, float* __restrict__ wn) {
-  const int64_t e = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (e >= E) return;
-  wn[e] = (dis[src[e]] * w[e * wstride]) * dis[tgt[e]];
+  MLAMG_GRID_STRIDE(e, E, kT, threadIdx.x) wn[e] = (dis[src[e]] * w[e * wstride]) * dis[tgt[e]];
 }
 
 // instance norm over nodes, per channel (affine False, biased variance, eps): a block per channel
@@ -132,49 +140,52 @@ __global__ void k_nnconv_msg(const int32_t* __restrict__ src, const float* __res
                              const float* __restrict__ c3, const float* __restrict__ X, int Fin,
                              int Fout, float* __restrict__ msg) {
   const int lane = threadIdx.x & 63, ob = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + lane;
   const int o0 = ob * 16;
   if (o0 >= Fout) return;
-  const bool live = e < E;
-  const int64_t ee = live ? e : 0;
-  float h1[4], h2[16];
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    float s = 0.0f;
-    for (int t = 0; t < fe; ++t) s = fmaf(L1[a * fe + t], ea[ee * fe + t], s);
-    h1[a] = fmaxf(s + c1[a], 0.0f);
-  }
-#pragma unroll
-  for (int a = 0; a < 16; ++a) {
-    float s = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) s = fmaf(L2[a * 4 + t], h1[t], s);
-    h2[a] = fmaxf(s + c2[a], 0.0f);
-  }
-  const float* xs = X + (int64_t)src[ee] * Fin;
-  float acc[16];
-#pragma unroll
-  for (int u = 0; u < 16; ++u) acc[u] = 0.0f;
   const int no = min(16, Fout - o0);
-  for (int i = 0; i < Fin; ++i) {
-    const float xi = xs[i];
+  MLAMG_GRID_STRIDE(e0, E, 64, 0) {  // a tile of 64 edges; the block strides together
+    const int64_t e = e0 + lane;
+    const bool live = e < E;
+    const int64_t ee = live ? e : 0;
+    float h1[4], h2[16];
 #pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      if (u < no) {
-        const int row = i * Fout + o0 + u;
-        const float* l = L3 + (int64_t)row * 16;
-        float s = 0.0f;
+    for (int a = 0; a < 4; ++a) {
+      float s = 0.0f;
+      for (int t = 0; t < fe; ++t) s = fmaf(L1[a * fe + t], ea[ee * fe + t], s);
+      h1[a] = fmaxf(s + c1[a], 0.0f);
+    }
 #pragma unroll
-        for (int t = 0; t < 16; ++t) s = fmaf(l[t], h2[t], s);
-        const float w = fmaxf(s + c3[row], 0.0f);
-        acc[u] = fmaf(xi, w, acc[u]);
+    for (int a = 0; a < 16; ++a) {
+      float s = 0.0f;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) s = fmaf(L2[a * 4 + t], h1[t], s);
+      h2[a] = fmaxf(s + c2[a], 0.0f);
+    }
+    const float* xs = X + (int64_t)src[ee] * Fin;
+    float acc[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) acc[u] = 0.0f;
+    for (int i = 0; i < Fin; ++i) {
+      const float xi = xs[i];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        if (u < no) {
+          const int row = i * Fout + o0 + u;
+          const float* l = L3 + (int64_t)row * 16;
+          float s = 0.0f;
+#pragma unroll
+          for (int t = 0; t < 16; ++t) s = fmaf(l[t], h2[t], s);
+          const float w = fmaxf(s + c3[row], 0.0f);
+          acc[u] = fmaf(xi, w, acc[u]);
+        }
       }
     }
-  }
-  if (!live) return;
+    if (live) {
 #pragma unroll
-  for (int u = 0; u < 16; ++u)
-    if (u < no) msg[e * Fout + o0 + u] = acc[u];
+      for (int u = 0; u < 16; ++u)
+        if (u < no) msg[e * Fout + o0 + u] = acc[u];
+    }
+  }
 }
 
 // out[i][o] = act(sum_{incoming e} msg[e][o] + root[i][o] + bias[o]) (+ R[i][o or 0])
@@ -182,20 +193,21 @@ __global__ void k_nnconv_aggr(const int32_t* __restrict__ tptr, const int32_t* _
                               const float* __restrict__ msg, const float* __restrict__ root,
                               const float* __restrict__ bias, int64_t n, int F, int act,
                               const float* __restrict__ R, int rc, float* __restrict__ Y) {
-  const int64_t i = (int64_t)blockIdx.x * (kT / 64) + threadIdx.x / 64;
   const int f = threadIdx.x & 63;
-  if (i >= n || f >= F) return;
-  float s = 0.0f;
-  for (int32_t q = tptr[i]; q < tptr[i + 1]; ++q) s += msg[(int64_t)teid[q] * F + f];
-  float y = (s + root[i * F + f]) + bias[f];
-  if (act == 1) y = fmaxf(y, 0.0f);
-  if (R) y = y + R[i * rc + (rc == 1 ? 0 : f)];
-  Y[i * F + f] = y;
+  if (f >= F) return;
+  MLAMG_GRID_STRIDE(i, n, kT / 64, threadIdx.x / 64) {
+    float s = 0.0f;
+    for (int32_t q = tptr[i]; q < tptr[i + 1]; ++q) s += msg[(int64_t)teid[q] * F + f];
+    float y = (s + root[i * F + f]) + bias[f];
+    if (act == 1) y = fmaxf(y, 0.0f);
+    if (R) y = y + R[i * rc + (rc == 1 ? 0 : f)];
+    Y[i * F + f] = y;
+  }
 }
 
 // smallEdgeModel (agg_interp.py:37-55) and MPNN's post-ops (:124-141): a wave per edge,
 //   in = [x_src (F) | x_tgt (F) | ea (fe)], h = relu(W1 in + b1) (H <= 64, lane o),
-//   h = LayerNorm(h) * g + beta (eps 1e-5, biased variance), y_c = W2[c] . h + b2[c] (C <= 2),
+//   h = LayerNorm(h) * g + beta (eps 1e-5, biased variance), y_c = W2[c] . h + b2[c] (C <= 4),
 //   out = act(y) (+ R[e][c or 0]).
 __global__ void k_edge_mlp(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt,
                            const float* __restrict__ X, int F, const float* __restrict__ ea,
@@ -209,47 +221,53 @@ __global__ void k_edge_mlp(const int32_t* __restrict__ src, const int32_t* __res
   for (int q = threadIdx.x; q < K * H; q += kT) w1t[q] = W1[(int64_t)(q % H) * K + q / H];
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const int64_t e = (int64_t)blockIdx.x * (kT / 64) + threadIdx.x / 64;
-  if (e >= E) return;
-  const float* xs = X + (int64_t)src[e] * F;
-  const float* xt = X + (int64_t)tgt[e] * F;
-  const float* a = ea + e * fe;
-  float h = 0.0f;
-  if (lane < H) {
-    for (int k = 0; k < F; ++k) h = fmaf(xs[k], w1t[k * H + lane], h);
-    for (int k = 0; k < F; ++k) h = fmaf(xt[k], w1t[(F + k) * H + lane], h);
-    for (int k = 0; k < fe; ++k) h = fmaf(a[k], w1t[(2 * F + k) * H + lane], h);
-    h = fmaxf(h + b1[lane], 0.0f);
-  }
-  const float mean = wsumf(lane < H ? h : 0.0f) / (float)H;
-  const float d = lane < H ? h - mean : 0.0f;
-  const float var = wsumf(d * d) / (float)H;
-  const float hn = lane < H ? (d / sqrtf(var + 1e-5f)) * g[lane] + beta[lane] : 0.0f;
-  for (int c = 0; c < C; ++c) {
-    float y = wsumf(lane < H ? hn * W2[c * H + lane] : 0.0f) + b2[c];
-    if (act == 1) y = fmaxf(y, 0.0f);
-    if (R) y = y + R[e * rc + (rc == 1 ? 0 : c)];
-    if (lane == 0) out[e * C + c] = y;
+  // e is the same in all 64 lanes of a wave, so a wave stays whole through the shuffles and
+  // leaves the loop (after the barrier above) as one
+  MLAMG_GRID_STRIDE(e, E, kT / 64, threadIdx.x / 64) {
+    const float* xs = X + (int64_t)src[e] * F;
+    const float* xt = X + (int64_t)tgt[e] * F;
+    const float* a = ea + e * fe;
+    float h = 0.0f;
+    if (lane < H) {
+      for (int k = 0; k < F; ++k) h = fmaf(xs[k], w1t[k * H + lane], h);
+      for (int k = 0; k < F; ++k) h = fmaf(xt[k], w1t[(F + k) * H + lane], h);
+      for (int k = 0; k < fe; ++k) h = fmaf(a[k], w1t[(2 * F + k) * H + lane], h);
+      h = fmaxf(h + b1[lane], 0.0f);
+    }
+    const float mean = wsumf(lane < H ? h : 0.0f) / (float)H;
+    const float d = lane < H ? h - mean : 0.0f;
+    const float var = wsumf(d * d) / (float)H;
+    const float hn = lane < H ? (d / sqrtf(var + 1e-5f)) * g[lane] + beta[lane] : 0.0f;
+    for (int c = 0; c < C; ++c) {
+      float y = wsumf(lane < H ? hn * W2[c * H + lane] : 0.0f) + b2[c];
+      if (act == 1) y = fmaxf(y, 0.0f);
+      if (R) y = y + R[e * rc + (rc == 1 ? 0 : c)];
+      if (lane == 0) out[e * C + c] = y;
+    }
   }
 }
 
-// top-k: keys ordered by descending score, then ascending node index
+// top-k: keys ordered by descending score (IEEE comparison: the two zeros are one score), then
+// ascending node index
 __global__ void k_topk_keys(const float* __restrict__ s, int64_t n, uint64_t* __restrict__ key) {
-  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (i >= n) return;
-  uint32_t u = __float_as_uint(s[i]);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending order of the float
-  key[i] = ((uint64_t)(~u) << 32) | (uint64_t)i;
+  MLAMG_GRID_STRIDE(i, n, kT, threadIdx.x) {
+    uint32_t u = __float_as_uint(s[i]);
+    if ((u << 1) == 0u) u = 0u;  // -0.0 == +0.0 is a tie: the index decides, not the sign bit
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending order of the float
+    key[i] = ((uint64_t)(~u) << 32) | (uint64_t)i;
+  }
 }
 __global__ void k_topk_mark(const uint64_t* __restrict__ key, int64_t k, float* __restrict__ vec,
                             int32_t* __restrict__ idx) {
-  const int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (q >= k) return;
-  const int32_t i = (int32_t)(key[q] & 0xffffffffu);
-  vec[i] = 1.0f;
-  if (idx) idx[q] = i;
+  MLAMG_GRID_STRIDE(q, k, kT, threadIdx.x) {
+    const int32_t i = (int32_t)(key[q] & 0xffffffffu);
+    vec[i] = 1.0f;
+    if (idx) idx[q] = i;
+  }
 }
 
+// The grid of a launch over n items, `per` to a block. The cap keeps the grid within HIP's limit
+// on threads per launch; MLAMG_GRID_STRIDE in every kernel covers the items beyond it.
 inline unsigned blocks(int64_t n, int per) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 1 << 20));
 }
@@ -264,7 +282,7 @@ extern "C" {
 int mlamg_gnn_linear(const float* X, int64_t M, int K, const float* W, const float* b, int N,
                      int act, float beta, const float* R, int rc, float* Y, void* stream) {
   MLAMG_REQUIRE(M >= 0 && K >= 1 && K <= 160 && N >= 1 && N <= 64, "linear: K <= 160, N <= 64");
-  MLAMG_REQUIRE(X && W && Y && (!R || rc == 1 || rc == N), "linear: bad arguments");
+  MLAMG_REQUIRE(W && (M == 0 || (X && Y)) && (!R || rc == 1 || rc == N), "linear: bad arguments");
   if (M == 0) return MLAMG_OK;
   int NP = 1;
   while (NP < N) NP <<= 1;
@@ -278,7 +296,8 @@ int mlamg_gnn_linear(const float* X, int64_t M, int K, const float* W, const flo
 int mlamg_gnn_gcn_norm(const int32_t* tptr, const int32_t* teid, const int32_t* src,
                        const int32_t* tgt, const float* w, int64_t n, int64_t E, float* dis_tmp,
                        float* wn, void* stream) {
-  MLAMG_REQUIRE(tptr && teid && src && tgt && w && dis_tmp && wn, "NULL argument");
+  MLAMG_REQUIRE(n >= 0 && E >= 0 && tptr && dis_tmp, "gcn_norm: NULL argument");
+  MLAMG_REQUIRE(E == 0 || (teid && src && tgt && w && wn), "gcn_norm: NULL edge argument");
   hipStream_t s = S(stream);
   hipLaunchKernelGGL(k_deg_isqrt, dim3(blocks(n, kT)), dim3(kT), 0, s, tptr, teid, w, n, dis_tmp);
   if (E > 0)
