@@ -280,6 +280,30 @@ int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, i
 int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_t* idx,
                    void* stream);
 
+/* A stack of nb graphs (FullAggNet.forward_batch): rows seg_ptr[g] .. seg_ptr[g + 1] are graph
+ * g's nodes. Every *_ptr array is int64[nb + 1] on the DEVICE and starts at 0; its *_host twin
+ * is the same array on the host, used to validate the call without reading the device back
+ * (NULL: the entry copies the device array back, one synchronisation). The two must be equal.
+ *
+ * InstanceNorm per graph and channel: segment g of Y is bitwise mlamg_gnn_instance_norm on rows
+ * seg_ptr[g] .. seg_ptr[g + 1] of X alone (the same strided double sums, wave sums and order of
+ * the wave partials, one workgroup per (graph, channel)). Does not synchronise with the host
+ * mirror given. Limits: every segment has >= 1 row, F >= 1 (EINVAL before any launch). */
+int mlamg_gnn_instance_norm_seg(const float* X, const int64_t* seg_ptr,
+                                const int64_t* seg_ptr_host, int64_t nb, int F, float eps,
+                                float* Y, void* stream);
+/* topk_vec per graph: vec[n] = 1 at the k_g = k_ptr[g + 1] - k_ptr[g] largest scores of segment
+ * g, 0 elsewhere; idx[k_ptr[g] .. k_ptr[g + 1]) = their node ids IN THE STACK, best first, in
+ * the order of mlamg_gnn_topk (score descending under IEEE comparison, -0.0 == +0.0, then node
+ * index ascending), so both are what mlamg_gnn_topk gives on the segment alone (idx + seg_ptr[g]).
+ * One stable radix sort over the stack (key: segment id, then score); its storage comes from a
+ * cached per-thread block, and with the host mirrors given the call neither allocates (after the
+ * first of its size) nor synchronises. Limits: 0 <= k_g <= n_g (n_g = 0 allowed), the stack has
+ * fewer than 2^31 - 1 rows; the order of NaN scores is unspecified. EINVAL before any launch. */
+int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_t* seg_ptr_host,
+                       const int64_t* k_ptr, const int64_t* k_ptr_host, int64_t nb, float* vec,
+                       int32_t* idx, void* stream);
+
 /* Seeded Bellman-Ford exactly as the reference's modified_bellman_ford (ns/lib/graph.py:7-53;
  * replaces that call at utils/evaluate_model.py:57, utils/evaluate_dataset.py:87): sweeps over
  * the edges (i -> j, weight g_ij rounded to fp32 like the torch COO values, ns/lib/sparse.py:28)
@@ -331,6 +355,35 @@ int mlamg_bf_canon_end(int32_t* cluster, int64_t n, void* stream);
  * sweeps (a negative cycle: pyamg would not return). Syncs. */
 int mlamg_bellman_ford_pyamg(const mlamg_csr* G, const int32_t* seeds, int32_t k, int fp64,
                              void* dist, int32_t* nearest, int32_t* sweeps_host, void* stream);
+
+/* The same sweep on a block-diagonal stack of nb graphs, one workgroup per graph: each walks the
+ * level schedule of its own diagonal block and sweeps to its own fixed point, so per graph the
+ * distances, the nearest seeds and the sweep count are bitwise mlamg_bellman_ford_pyamg on that
+ * graph alone (nearest seeds as node ids in the stack).
+ *
+ * plan_create reads G's pattern once on the host (the only host pass; syncs) and keeps, per
+ * graph, its rows in level order and its level pointers. seg_ptr as in mlamg_gnn_*_seg above
+ * (graphs of 0 rows allowed). EINVAL if seg_ptr does not cover G's rows, a graph has more than
+ * 2^18 rows, or a stored entry couples two graphs (the message names the row).
+ *
+ * The run takes any G with the plan's pattern (n_rows and nnz are checked) and the seeds of
+ * graph g in seeds[seed_ptr[g] .. seed_ptr[g + 1]) as node ids in the stack. dist / nearest /
+ * fp64 as in mlamg_bellman_ford_pyamg; sweeps_host[nb] (nullable). A seed outside its own graph
+ * is found on the device before anything is written: EINVAL, outputs untouched. A graph without
+ * a fixed point after n_g + 2 sweeps (a negative cycle) gives EINVAL naming the first such graph;
+ * the others' results are complete. Launches and the one read-back (2 nb + 1 words) do not depend
+ * on nb. While it sweeps, a graph's distances and labels are kept in LDS when the largest graph's
+ * fit in 64 KiB (8,192 rows in float32, 5,461 in float64; MLAMG_BF_SEG_LDS=0 keeps them in global
+ * memory): same bits, 14-18 % faster. Syncs. */
+typedef struct mlamg_bf_seg_plan mlamg_bf_seg_plan;
+int mlamg_bellman_ford_pyamg_seg_plan_create(const mlamg_csr* G, const int64_t* seg_ptr,
+                                             const int64_t* seg_ptr_host, int64_t nb,
+                                             mlamg_bf_seg_plan** out, void* stream);
+int mlamg_bellman_ford_pyamg_seg_plan_destroy(mlamg_bf_seg_plan* plan);
+int mlamg_bellman_ford_pyamg_seg(const mlamg_bf_seg_plan* plan, const mlamg_csr* G,
+                                 const int32_t* seeds, const int64_t* seed_ptr,
+                                 const int64_t* seed_ptr_host, int fp64, void* dist,
+                                 int32_t* nearest, int32_t* sweeps_host, void* stream);
 
 /* out[0..k) (DEVICE int32) = np.random.RandomState(seed).permutation(n)[:k] bit for bit (numpy's
  * legacy MT19937 + Fisher-Yates; the seeds of ns/lib/graph.py:230-231 and

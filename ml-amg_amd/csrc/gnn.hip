@@ -128,6 +128,44 @@ __global__ void k_inorm(const float* __restrict__ X, int64_t n, int F, float eps
   for (int64_t i = threadIdx.x; i < n; i += kT) Y[i * F + f] = (X[i * F + f] - mf) * inv;
 }
 
+// the same over a stack of graphs: item = (segment g, channel f), a block per item; inside the
+// segment (rows seg[g] .. seg[g + 1]) the loop bodies, the wave sums and the order over the four
+// wave partials are k_inorm's on that segment alone, so the result is too, bit for bit
+__global__ void k_inorm_seg(const float* __restrict__ Xs, const int64_t* __restrict__ seg,
+                            int64_t items, int F, float eps, float* __restrict__ Ys) {
+  __shared__ double red[kT / 64];
+  MLAMG_GRID_STRIDE(it, items, 1, 0) {  // `it` is block-uniform: the block strides together
+    const int64_t g = it / F;
+    const int f = (int)(it % F);
+    const int64_t a = seg[g], n = seg[g + 1] - a;
+    const float* X = Xs + a * F;
+    float* Y = Ys + a * F;
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kT) s += X[i * F + f];
+    s = wsum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = s;
+    __syncthreads();
+    double tot = 0.0;
+    for (int w = 0; w < kT / 64; ++w) tot += red[w];
+    const double mean = tot / (double)n;
+    __syncthreads();
+    double v = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kT) {
+      const double d = X[i * F + f] - mean;
+      v += d * d;
+    }
+    v = wsum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = v;
+    __syncthreads();
+    double vt = 0.0;
+    for (int w = 0; w < kT / 64; ++w) vt += red[w];
+    const float inv = (float)(1.0 / sqrt(vt / (double)n + (double)eps));
+    const float mf = (float)mean;
+    for (int64_t i = threadIdx.x; i < n; i += kT) Y[i * F + f] = (X[i * F + f] - mf) * inv;
+    __syncthreads();  // every wave has read red before the next item overwrites it
+  }
+}
+
 // NNConv messages, the edge network fused in: per edge e (features ea[e][0..fe)),
 //   h1 = relu(L1 ea + c1) (4), h2 = relu(L2 h1 + c2) (16), W_e = relu(L3 h2 + c3) [Fin x Fout],
 //   msg[e][o] = sum_i x_src[i] W_e[i][o]   (NNConv.message: x_j @ weight.view(-1, in, out))
@@ -266,6 +304,65 @@ __global__ void k_topk_mark(const uint64_t* __restrict__ key, int64_t k, float* 
   }
 }
 
+// top-k per segment of a stack. The segment g with ptr[g] <= t < ptr[g + 1] (empty segments are
+// skipped): the last g in [0, nb) with ptr[g] <= t.
+__device__ __forceinline__ int64_t seg_of(const int64_t* __restrict__ ptr, int64_t nb, int64_t t) {
+  int64_t lo = 0, hi = nb - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (ptr[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// key = segment id | k_topk_keys' descending-score word; the node index rides along as the
+// value. The radix sort is stable and the input is in ascending node order, so equal scores of a
+// segment stay in ascending index: the order of k_topk_keys inside every segment.
+__global__ void k_topk_seg_keys(const float* __restrict__ s, const int64_t* __restrict__ seg,
+                                int64_t nb, int64_t n, uint64_t* __restrict__ key,
+                                int32_t* __restrict__ val) {
+  MLAMG_GRID_STRIDE(i, n, kT, threadIdx.x) {
+    uint32_t u = __float_as_uint(s[i]);
+    if ((u << 1) == 0u) u = 0u;
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    key[i] = ((uint64_t)seg_of(seg, nb, i) << 32) | (uint64_t)(~u);
+    val[i] = (int32_t)i;
+  }
+}
+// entry t of idx belongs to segment g = seg_of(kptr, t) and is that segment's (t - kptr[g])-th
+// best: position seg[g] + t - kptr[g] of the sorted stack
+__global__ void k_topk_seg_mark(const int32_t* __restrict__ sorted, const int64_t* __restrict__ seg,
+                                const int64_t* __restrict__ kptr, int64_t nb, int64_t K,
+                                float* __restrict__ vec, int32_t* __restrict__ idx) {
+  MLAMG_GRID_STRIDE(t, K, kT, threadIdx.x) {
+    const int64_t g = seg_of(kptr, nb, t);
+    const int32_t i = sorted[seg[g] + (t - kptr[g])];
+    vec[i] = 1.0f;
+    idx[t] = i;
+  }
+}
+
+// a segment pointer array on the host: the caller's mirror, or a copy of the device array (one
+// synchronisation). Checks ptr[0] == 0 and that no step is below `min_step`.
+int host_ptr(const int64_t* dev, const int64_t* host, int64_t nb, int64_t min_step, hipStream_t s,
+             std::vector<int64_t>& out, const char* what) {
+  out.assign((size_t)nb + 1, 0);
+  if (host) {
+    std::copy(host, host + nb + 1, out.begin());
+  } else {
+    MLAMG_HIP(hipMemcpyAsync(out.data(), dev, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
+    MLAMG_HIP(hipStreamSynchronize(s));
+  }
+  bool ok = out[0] == 0;
+  for (int64_t g = 0; g < nb; ++g) ok = ok && out[g + 1] - out[g] >= min_step;
+  if (!ok) {
+    set_error(std::string(what) + (min_step > 0 ? ": offsets must start at 0 and every segment "
+                                                  "needs at least one row"
+                                                : ": offsets must start at 0 and not decrease"));
+    return MLAMG_EINVAL;
+  }
+  return MLAMG_OK;
+}
+
 // The grid of a launch over n items, `per` to a block. The cap keeps the grid within HIP's limit
 // on threads per launch; MLAMG_GRID_STRIDE in every kernel covers the items beyond it.
 inline unsigned blocks(int64_t n, int per) {
@@ -320,6 +417,67 @@ int mlamg_gnn_propagate(const int32_t* tptr, const int32_t* teid, const int32_t*
 int mlamg_gnn_instance_norm(const float* X, int64_t n, int F, float eps, float* Y, void* stream) {
   MLAMG_REQUIRE(n >= 1 && F >= 1, "instance norm: empty input");
   hipLaunchKernelGGL(k_inorm, dim3(F), dim3(kT), 0, S(stream), X, n, F, eps, Y);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int mlamg_gnn_instance_norm_seg(const float* X, const int64_t* seg_ptr,
+                                const int64_t* seg_ptr_host, int64_t nb, int F, float eps,
+                                float* Y, void* stream) {
+  MLAMG_REQUIRE(nb >= 0 && F >= 1, "instance norm (segmented): nb >= 0, F >= 1");
+  if (nb == 0) return MLAMG_OK;
+  MLAMG_REQUIRE(X && Y && seg_ptr, "instance norm (segmented): NULL argument");
+  MLAMG_REQUIRE(nb <= INT64_MAX / F, "instance norm (segmented): nb * F overflows");
+  std::vector<int64_t> seg;
+  MLAMG_TRY(host_ptr(seg_ptr, seg_ptr_host, nb, 1, S(stream), seg, "instance norm (segmented)"));
+  const int64_t items = nb * (int64_t)F;
+  hipLaunchKernelGGL(k_inorm_seg, dim3(blocks(items, 1)), dim3(kT), 0, S(stream), X, seg_ptr,
+                     items, F, eps, Y);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_t* seg_ptr_host,
+                       const int64_t* k_ptr, const int64_t* k_ptr_host, int64_t nb, float* vec,
+                       int32_t* idx, void* stream) {
+  MLAMG_REQUIRE(nb >= 0, "topk (segmented): negative segment count");
+  if (nb == 0) return MLAMG_OK;
+  MLAMG_REQUIRE(seg_ptr && k_ptr, "topk (segmented): NULL argument");
+  hipStream_t s = S(stream);
+  std::vector<int64_t> seg, kp;
+  MLAMG_TRY(host_ptr(seg_ptr, seg_ptr_host, nb, 0, s, seg, "topk (segmented) seg_ptr"));
+  MLAMG_TRY(host_ptr(k_ptr, k_ptr_host, nb, 0, s, kp, "topk (segmented) k_ptr"));
+  for (int64_t g = 0; g < nb; ++g)
+    MLAMG_REQUIRE(kp[g + 1] - kp[g] <= seg[g + 1] - seg[g],
+                  "topk (segmented): a segment asks for more than its own rows (k_g <= n_g)");
+  const int64_t n = seg[nb], K = kp[nb];
+  MLAMG_REQUIRE(n < INT32_MAX, "topk (segmented): stack too large for int32 node ids");
+  if (n == 0) return MLAMG_OK;
+  MLAMG_REQUIRE(scores && vec && (K == 0 || idx), "topk (segmented): NULL argument");
+  int seg_bits = 0;
+  while ((int64_t(1) << seg_bits) < nb) ++seg_bits;
+  // one cached block: keys in | keys out | values in | values out | the sort's own storage
+  size_t tb = 0;
+  MLAMG_HIP(rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                      (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, 0,
+                                      32 + seg_bits, s));
+  const size_t kb = (sizeof(uint64_t) * (size_t)n + 255) / 256 * 256;
+  const size_t vb = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
+  char* base = static_cast<char*>(scratch(2 * kb + 2 * vb + tb + 256, 19));
+  MLAMG_REQUIRE(base, "topk (segmented): scratch allocation failed");
+  uint64_t* k0 = reinterpret_cast<uint64_t*>(base);
+  uint64_t* k1 = reinterpret_cast<uint64_t*>(base + kb);
+  int32_t* v0 = reinterpret_cast<int32_t*>(base + 2 * kb);
+  int32_t* v1 = reinterpret_cast<int32_t*>(base + 2 * kb + vb);
+  void* tmp = base + 2 * kb + 2 * vb;
+  hipLaunchKernelGGL(k_topk_seg_keys, dim3(blocks(n, kT)), dim3(kT), 0, s, scores, seg_ptr, nb, n,
+                     k0, v0);
+  MLAMG_HIP(hipGetLastError());
+  MLAMG_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, (size_t)n, 0, 32 + seg_bits, s));
+  MLAMG_HIP(hipMemsetAsync(vec, 0, sizeof(float) * n, s));
+  if (K > 0)
+    hipLaunchKernelGGL(k_topk_seg_mark, dim3(blocks(K, kT)), dim3(kT), 0, s, v1, seg_ptr, k_ptr, nb,
+                       K, vec, idx);
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;
 }

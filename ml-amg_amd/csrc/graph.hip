@@ -332,6 +332,87 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_pyamg(const int32_t* __restrict
   }
 }
 
+// The same on a block-diagonal stack: workgroup g owns rows seg[g] .. seg[g + 1], its seeds
+// seeds[sptr[g] .. sptr[g + 1]) and levels lptr[loff[g] .. loff[g + 1]) (positions into `rows`).
+// It initialises, seeds and sweeps its own block to its own fixed point with k_bf_pyamg's loop;
+// pull_row reads only the block's own x and z (G is block diagonal), so every (x, z) and the
+// sweep count are the single graph's. out[2 g] = sweeps, out[2 g + 1] = unconverged. *bad (set by
+// k_bf_seg_check_seeds) makes every workgroup leave before it writes anything.
+// LDS: the block's x and z live in LDS (cap rows each) during the sweeps and are written out at
+// the end; the values and their order are the same, only where they are kept differs.
+template <typename T, bool LDS>
+__global__ __launch_bounds__(kBfBlock) void k_bf_pyamg_seg(
+    const int32_t* __restrict__ ip, const int32_t* __restrict__ ij, const double* __restrict__ ax,
+    const int32_t* __restrict__ seg, const int32_t* __restrict__ loff,
+    const int32_t* __restrict__ lptr, const int32_t* __restrict__ rows,
+    const int32_t* __restrict__ seeds, const int64_t* __restrict__ sptr, T big, T* xg, int32_t* zg,
+    int32_t cap, const int32_t* __restrict__ bad, int32_t* __restrict__ out) {
+  __shared__ int32_t changed;
+  extern __shared__ double bf_lds[];  // LDS: x[cap] | z[cap]
+  if (*bad) return;  // the same word for every thread: the block leaves as one
+  const int32_t g = blockIdx.x;
+  const int32_t r0 = seg[g], r1 = seg[g + 1];
+  // indexed by node id in the stack either way: the LDS copies are offset by the block's first row
+  T* x = LDS ? reinterpret_cast<T*>(bf_lds) - r0 : xg;
+  int32_t* z = LDS ? reinterpret_cast<int32_t*>(reinterpret_cast<T*>(bf_lds) + cap) - r0 : zg;
+  for (int32_t i = r0 + (int32_t)threadIdx.x; i < r1; i += kBfBlock) {
+    x[i] = big;
+    z[i] = -1;
+  }
+  __syncthreads();
+  for (int64_t t = sptr[g] + threadIdx.x; t < sptr[g + 1]; t += kBfBlock) {
+    const int32_t sd = seeds[t];
+    x[sd] = T(0);
+    z[sd] = sd;
+  }
+  __syncthreads();
+  const int32_t* lp = lptr + loff[g];
+  const int32_t n_levels = loff[g + 1] - loff[g] - 1;
+  const int32_t max_sweeps = r1 - r0 + 2;
+  int32_t sweeps = 0, c = 0;
+  do {
+    if (threadIdx.x == 0) changed = 0;
+    __syncthreads();
+    int any = 0;
+    for (int32_t l = 0; l < n_levels; ++l) {
+      const int32_t a = lp[l], e = lp[l + 1];
+      for (int32_t t = a + (int32_t)threadIdx.x; t < e; t += kBfBlock)
+        any |= pull_row<T>(rows[t], ip, ij, ax, x, z);
+      __syncthreads();
+    }
+    if (any) changed = 1;
+    __syncthreads();
+    ++sweeps;
+    c = changed;
+    __syncthreads();
+  } while (c && sweeps < max_sweeps);
+  if (LDS)  // the loop's last barrier is behind every write
+    for (int32_t i = r0 + (int32_t)threadIdx.x; i < r1; i += kBfBlock) {
+      xg[i] = x[i];
+      zg[i] = z[i];
+    }
+  if (threadIdx.x == 0) {
+    out[2 * g] = sweeps;
+    out[2 * g + 1] = c;
+  }
+}
+
+// seed t belongs to the graph g with sptr[g] <= t < sptr[g + 1] and must be one of its rows
+__global__ void k_bf_seg_check_seeds(const int32_t* __restrict__ seeds,
+                                     const int64_t* __restrict__ sptr,
+                                     const int32_t* __restrict__ seg, int32_t nb, int64_t K,
+                                     int32_t* __restrict__ bad) {
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
+    int32_t lo = 0, hi = nb - 1;
+    while (lo < hi) {
+      const int32_t mid = (lo + hi + 1) >> 1;
+      if (sptr[mid] <= t) lo = mid; else hi = mid - 1;
+    }
+    const int32_t sd = seeds[t];
+    if (sd < seg[lo] || sd >= seg[lo + 1]) *bad = 1;
+  }
+}
+
 // one level of the pull sweep over the whole GPU (graphs above kSeqOneBlockMax rows)
 template <typename T>
 __global__ void k_bfp_level(const int32_t* __restrict__ ip, const int32_t* __restrict__ ij,
@@ -666,7 +747,42 @@ static int run_push(const SeqPlan& P, float* d, int32_t* z, float* dm, int32_t* 
 
 }  // namespace mlamg
 
+// the level schedules of a block-diagonal stack, one per graph, as one int32 device array:
+// seg[nb + 1] | loff[nb + 1] | lptr[loff[nb]] | rows[n] (level order inside each graph) |
+// out[2 nb] (sweeps, unconverged per graph) | bad[1]
+struct mlamg_bf_seg_plan {
+  int32_t* d = nullptr;
+  int64_t n = 0, nnz = 0, nb = 0;
+  size_t o_loff = 0, o_lptr = 0, o_rows = 0, o_out = 0;
+  int32_t max_rows = 0;  // of one graph
+  ~mlamg_bf_seg_plan() {
+    if (d) (void)hipFree(d);
+  }
+};
+
 using namespace mlamg;
+
+// x and z of every graph in LDS while it sweeps, when the largest graph's fit in the 64 KiB a
+// launch gets without opting in (8,192 rows in float32, 5,461 in float64); MLAMG_BF_SEG_LDS=0|1
+// forces the choice where it applies (the A/B knob of tools/bench_gnn_batch.py; tests run both).
+template <typename T>
+static void launch_bf_seg(const mlamg_bf_seg_plan* P, const mlamg_csr* G, const int32_t* seeds,
+                          const int64_t* seed_ptr, T big, T* x, int32_t* z, hipStream_t s) {
+  const size_t bytes = (size_t)P->max_rows * (sizeof(T) + sizeof(int32_t));
+  const char* force = std::getenv("MLAMG_BF_SEG_LDS");
+  const bool lds = bytes <= (size_t(64) << 10) && !(force && force[0] == '0');
+  int32_t* out = P->d + P->o_out;
+  if (lds)
+    hipLaunchKernelGGL((k_bf_pyamg_seg<T, true>), dim3((unsigned)P->nb), dim3(kBfBlock), bytes, s,
+                       G->indptr, G->indices, G->data, P->d, P->d + P->o_loff, P->d + P->o_lptr,
+                       P->d + P->o_rows, seeds, seed_ptr, big, x, z, P->max_rows, out + 2 * P->nb,
+                       out);
+  else
+    hipLaunchKernelGGL((k_bf_pyamg_seg<T, false>), dim3((unsigned)P->nb), dim3(kBfBlock), 0, s,
+                       G->indptr, G->indices, G->data, P->d, P->d + P->o_loff, P->d + P->o_lptr,
+                       P->d + P->o_rows, seeds, seed_ptr, big, x, z, P->max_rows, out + 2 * P->nb,
+                       out);
+}
 
 extern "C" {
 
@@ -830,6 +946,148 @@ int mlamg_bellman_ford_pyamg(const mlamg_csr* G, const int32_t* seeds, int32_t k
     MLAMG_TRY(run_pull<float>(G, P, x, nearest, s, &sweeps));
   }
   if (sweeps_host) *sweeps_host = sweeps;
+  return MLAMG_OK;
+}
+
+int mlamg_bellman_ford_pyamg_seg_plan_create(const mlamg_csr* G, const int64_t* seg_ptr,
+                                             const int64_t* seg_ptr_host, int64_t nb,
+                                             mlamg_bf_seg_plan** out, void* stream) {
+  MLAMG_REQUIRE(G && out && nb >= 1 && (seg_ptr || seg_ptr_host), "NULL argument");
+  MLAMG_REQUIRE(G->n_rows == G->n_cols, "graph must be square");
+  MLAMG_REQUIRE(nb < INT32_MAX, "too many graphs");
+  hipStream_t s = S(stream);
+  const int64_t n = G->n_rows;
+  std::vector<int64_t> seg((size_t)nb + 1, 0);
+  if (seg_ptr_host) {
+    std::copy(seg_ptr_host, seg_ptr_host + nb + 1, seg.begin());
+  } else {
+    MLAMG_HIP(hipMemcpyAsync(seg.data(), seg_ptr, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
+    MLAMG_HIP(hipStreamSynchronize(s));
+  }
+  MLAMG_REQUIRE(seg[0] == 0 && seg[nb] == n, "seg_ptr must run from 0 to the number of rows");
+  for (int64_t g = 0; g < nb; ++g) {
+    MLAMG_REQUIRE(seg[g + 1] >= seg[g], "seg_ptr must not decrease");
+    if (seg[g + 1] - seg[g] > kSeqOneBlockMax) {
+      set_error("bellman_ford_pyamg_seg: graph " + std::to_string(g) + " has " +
+                std::to_string(seg[g + 1] - seg[g]) + " rows, above the one-workgroup limit " +
+                std::to_string(kSeqOneBlockMax));
+      return MLAMG_EINVAL;
+    }
+  }
+  std::vector<int32_t> ip, ij;
+  MLAMG_TRY(fetch_pattern(G, s, ip, ij, nullptr));
+  // build_pull_plan's rule; a block-diagonal pattern couples a row only to rows of its own
+  // graph, so the levels of a block are those of the graph alone
+  std::vector<int32_t> level(n, 0), req(n, 0), nlev((size_t)nb, 0);
+  for (int64_t g = 0; g < nb; ++g) {
+    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) {
+      int32_t L = req[i];
+      for (int32_t q = ip[i]; q < ip[i + 1]; ++q) {
+        const int64_t j = ij[q];
+        if (j < seg[g] || j >= seg[g + 1]) {
+          set_error("bellman_ford_pyamg_seg: not block diagonal: row " + std::to_string(i) +
+                    " of graph " + std::to_string(g) + " is coupled to column " + std::to_string(j));
+          return MLAMG_EINVAL;
+        }
+        if (j < i) L = std::max(L, level[j] + 1);
+      }
+      level[i] = L;
+      for (int32_t q = ip[i]; q < ip[i + 1]; ++q)
+        if (ij[q] > i) req[ij[q]] = std::max(req[ij[q]], L + 1);
+      nlev[g] = std::max(nlev[g], L + 1);
+    }
+  }
+  // seg[nb + 1] | loff[nb + 1] | lptr[sum (nlev_g + 1)] | rows[n] | out[2 nb] | bad[1]
+  std::vector<int32_t> loff((size_t)nb + 1, 0);
+  for (int64_t g = 0; g < nb; ++g) loff[g + 1] = loff[g] + nlev[g] + 1;
+  const size_t o_loff = (size_t)nb + 1, o_lptr = 2 * ((size_t)nb + 1);
+  const size_t o_rows = o_lptr + (size_t)loff[nb], o_out = o_rows + (size_t)n;
+  std::vector<int32_t> plan(o_out + 2 * (size_t)nb + 1, 0);
+  for (int64_t g = 0; g <= nb; ++g) {
+    plan[g] = (int32_t)seg[g];
+    plan[o_loff + g] = loff[g];
+  }
+  for (int64_t g = 0; g < nb; ++g) {
+    int32_t* lp = plan.data() + o_lptr + loff[g];  // counts, then positions into rows
+    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) lp[level[i] + 1]++;
+    lp[0] = (int32_t)seg[g];
+    for (int32_t l = 0; l < nlev[g]; ++l) lp[l + 1] += lp[l];
+    std::vector<int32_t> fill(lp, lp + nlev[g]);
+    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) plan[o_rows + fill[level[i]]++] = (int32_t)i;
+  }
+  auto* P = new mlamg_bf_seg_plan();
+  P->n = n;
+  P->nnz = G->nnz;
+  P->nb = nb;
+  P->o_loff = o_loff;
+  P->o_lptr = o_lptr;
+  P->o_rows = o_rows;
+  P->o_out = o_out;
+  for (int64_t g = 0; g < nb; ++g)
+    P->max_rows = std::max<int32_t>(P->max_rows, (int32_t)(seg[g + 1] - seg[g]));
+  hipError_t e = hipMalloc(&P->d, sizeof(int32_t) * plan.size());
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(P->d, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);  // `plan` is pageable and goes out of scope
+  if (e != hipSuccess) {
+    delete P;
+    set_error(std::string("bellman_ford_pyamg_seg plan: ") + hipGetErrorString(e));
+    return MLAMG_EHIP;
+  }
+  *out = P;
+  return MLAMG_OK;
+}
+
+int mlamg_bellman_ford_pyamg_seg_plan_destroy(mlamg_bf_seg_plan* plan) {
+  delete plan;
+  return MLAMG_OK;
+}
+
+int mlamg_bellman_ford_pyamg_seg(const mlamg_bf_seg_plan* P, const mlamg_csr* G,
+                                 const int32_t* seeds, const int64_t* seed_ptr,
+                                 const int64_t* seed_ptr_host, int fp64, void* dist,
+                                 int32_t* nearest, int32_t* sweeps_host, void* stream) {
+  MLAMG_REQUIRE(P && G && seed_ptr, "NULL argument");
+  MLAMG_REQUIRE(fp64 == 0 || fp64 == 1, "fp64 must be 0 (float32 graph) or 1 (float64 graph)");
+  MLAMG_REQUIRE(G->n_rows == P->n && G->n_cols == P->n && G->nnz == P->nnz,
+                "bellman_ford_pyamg_seg: G does not have the plan's pattern");
+  hipStream_t s = S(stream);
+  const int64_t nb = P->nb;
+  std::vector<int64_t> sp((size_t)nb + 1, 0);
+  if (seed_ptr_host) {
+    std::copy(seed_ptr_host, seed_ptr_host + nb + 1, sp.begin());
+  } else {
+    MLAMG_HIP(hipMemcpyAsync(sp.data(), seed_ptr, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
+    MLAMG_HIP(hipStreamSynchronize(s));
+  }
+  MLAMG_REQUIRE(sp[0] == 0, "seed_ptr must start at 0");
+  for (int64_t g = 0; g < nb; ++g) MLAMG_REQUIRE(sp[g + 1] >= sp[g], "seed_ptr must not decrease");
+  const int64_t K = sp[nb];
+  MLAMG_REQUIRE((P->n == 0 || (dist && nearest)) && (K == 0 || seeds), "NULL argument");
+  int32_t* out = P->d + P->o_out;
+  int32_t* bad = out + 2 * nb;
+  MLAMG_HIP(hipMemsetAsync(out, 0, sizeof(int32_t) * (2 * nb + 1), s));
+  if (K)
+    hipLaunchKernelGGL(k_bf_seg_check_seeds,
+                       dim3((unsigned)std::min<int64_t>((K + 255) / 256, 1 << 16)), dim3(256), 0, s,
+                       seeds, seed_ptr, P->d, (int32_t)nb, K, bad);
+  if (fp64)
+    launch_bf_seg<double>(P, G, seeds, seed_ptr, DBL_MAX, static_cast<double*>(dist), nearest, s);
+  else
+    launch_bf_seg<float>(P, G, seeds, seed_ptr, FLT_MAX, static_cast<float*>(dist), nearest, s);
+  MLAMG_HIP(hipGetLastError());
+  std::vector<int32_t> res(2 * (size_t)nb + 1, 0);
+  MLAMG_HIP(hipMemcpyAsync(res.data(), out, sizeof(int32_t) * res.size(), hipMemcpyDeviceToHost, s));
+  MLAMG_HIP(hipStreamSynchronize(s));
+  MLAMG_REQUIRE(res[2 * nb] == 0, "bellman_ford_pyamg_seg: a seed lies outside its own graph");
+  if (sweeps_host)
+    for (int64_t g = 0; g < nb; ++g) sweeps_host[g] = res[2 * g];
+  for (int64_t g = 0; g < nb; ++g)
+    if (res[2 * g + 1]) {
+      set_error("bellman_ford_pyamg_seg: graph " + std::to_string(g) +
+                ": no fixed point after n + 2 sweeps (negative cycle)");
+      return MLAMG_EINVAL;
+    }
   return MLAMG_OK;
 }
 

@@ -11,6 +11,7 @@ Mirrors the reference modules on the hot path:
                                                   strength of connection on the device)
   mlamg.preconditioner  <- ns/preconditioner     (MLAMG PC: initialize/update/apply)
   mlamg.gnn             <- ns/model/agg_interp.py (FullAggNet inference: AggNet, MPNN)
+  mlamg.fitness         <- utils/train_dataset.py:81-138 (the GA's conv-factor fitness, batched)
   mlamg.loss            <- ns/model/loss.py      (amg_loss on a block of test vectors, fp64, and
                                                   its gradient with respect to P's values)
   mlamg.hierarchy       multilevel device hierarchy + V-cycle executor (precondition/solve)
@@ -25,7 +26,7 @@ import importlib
 __version__ = "0.1.0"
 
 _SUBMODULES = ("multigrid", "graph", "sparse", "strength", "gnn", "hierarchy",
-               "preconditioner", "problems", "gridio", "distributed", "loss", "_lib")
+               "preconditioner", "problems", "gridio", "distributed", "loss", "fitness", "_lib")
 
 
 def __getattr__(name):

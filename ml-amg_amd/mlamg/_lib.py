@@ -128,6 +128,14 @@ SIGNATURES = {
                                    c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_int,
                                    c_vp, c_vp]),
     "mlamg_gnn_topk": (c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    # a stack of graphs (FullAggNet.forward_batch): device offsets + their host mirrors
+    "mlamg_gnn_instance_norm_seg": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_float, c_vp,
+                                            c_vp]),
+    "mlamg_gnn_topk_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "mlamg_bellman_ford_pyamg_seg_plan_create": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vpp, c_vp]),
+    "mlamg_bellman_ford_pyamg_seg_plan_destroy": (c_int, [c_vp]),
+    "mlamg_bellman_ford_pyamg_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,
+                                             c_vp, c_vp]),
     "mlamg_bellman_ford": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, P_i32, c_vp]),
     "mlamg_bellman_ford_canon": (c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, P_i32, c_vp]),
     "mlamg_bellman_ford_pyamg": (c_int, [c_vp, c_vp, c_i32, c_int, c_vp, c_vp, P_i32, c_vp]),

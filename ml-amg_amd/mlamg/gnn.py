@@ -10,6 +10,10 @@ not on torch ops. torch_geometric is absent: its layers (TAGConv K=3 with gcn_no
 'add' with root weight, InstanceNorm) are restated from its 2.x semantics; the reference's
 trained weights are not shipped, so parity is against oracle/gnn_ref.py (a torch restatement
 of the same layers) at seeded weights — parity unpinned with respect to torch_geometric itself.
+
+`GraphBatch` + `FullAggNet.forward_batch` run the same forward pass on many graphs at once (the
+graphs stacked block-diagonally, the per-graph steps as segmented kernels), every graph's
+tensors bitwise its own `forward`.
 """
 from __future__ import annotations
 
@@ -90,6 +94,130 @@ class Graph:
         return self._gcn
 
 
+class SegPtr:
+    """Segment offsets of a stack, int64[nb + 1] from 0: on the host and on the device (the C
+    entry points validate the host copy, the kernels read the device copy)."""
+
+    def __init__(self, host, device):
+        self.host = np.ascontiguousarray(host, dtype=np.int64)
+        self.dev = torch.as_tensor(self.host).to(device)
+
+    @property
+    def host_ptr(self):
+        return self.host.ctypes.data_as(ctypes.c_void_p)
+
+
+class GraphBatch:
+    """Many graphs as one block-diagonal stack, built once per dataset: the fields of
+    Graph(scipy.sparse.block_diag(As)) — node ids of graph g offset by seg.host[g], edges in
+    graph order — except x, which carries 1/n_g on graph g's nodes, plus the node and edge
+    segment pointers (seg, eseg), every node's graph id (node_gid), the cached gcn_norm weights
+    and the cached Bellman-Ford level plan (created on first use, on the device).
+
+    Every GNN kernel but InstanceNorm and top-k produces a row or an edge from its own inputs in
+    an order that does not depend on where the item sits, so on this stack it gives the bits of
+    the single call; the two exceptions and pyamg's sequential sweep have segmented kernels
+    (FullAggNet.forward_batch). Every matrix must have canonical format (sorted, duplicate-free
+    rows): pyamg would sweep a re-sorted, duplicate-summed copy, which stays with forward()."""
+
+    def __init__(self, As, device=None):
+        mats = []
+        for i, A in enumerate(As):
+            A = sp.csr_matrix(A)
+            if A.shape[0] != A.shape[1] or A.shape[0] < 1:
+                raise ValueError(f"matrix {i} of the batch is not square and non-empty: {A.shape}")
+            if not A.has_canonical_format:
+                raise ValueError(f"matrix {i} of the batch has no canonical format (unsorted or "
+                                 "duplicate entries); run it through forward() on its own")
+            mats.append(A)
+        if not mats:
+            raise ValueError("empty batch")
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        dev = torch.device(dev)
+        sizes = np.array([A.shape[0] for A in mats], dtype=np.int64)
+        nnzs = np.array([A.nnz for A in mats], dtype=np.int64)
+        seg = np.concatenate([[0], np.cumsum(sizes)])
+        eseg = np.concatenate([[0], np.cumsum(nnzs)])
+        n, E = int(seg[-1]), int(eseg[-1])
+        if n >= 2 ** 31 - 1 or E >= 2 ** 31 - 1:
+            raise ValueError("batch exceeds the int32 index range")
+        indptr = np.concatenate([[0]] + [A.indptr[1:].astype(np.int64) + eseg[g]
+                                         for g, A in enumerate(mats)]).astype(np.int32)
+        tgt = np.concatenate([A.indices.astype(np.int64) + seg[g]
+                              for g, A in enumerate(mats)]).astype(np.int32)
+        src = np.repeat(np.arange(n, dtype=np.int32), np.diff(indptr))
+        ea = np.concatenate([np.abs(A.data.astype(np.float32)) for A in mats])[:, None]
+        order = np.argsort(tgt, kind="stable")
+        tptr = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum(np.bincount(tgt, minlength=n), out=tptr[1:])
+        self.As = mats
+        self.nb, self.n, self.E, self.fe = len(mats), n, E, 1
+        self.sizes = sizes
+        self.device = dev
+        self.seg, self.eseg = SegPtr(seg, dev), SegPtr(eseg, dev)
+        self.node_gid = torch.as_tensor(np.repeat(np.arange(self.nb, dtype=np.int64), sizes),
+                                        device=dev)
+        self.crow = torch.as_tensor(indptr, device=dev)
+        self.src = torch.as_tensor(src, device=dev)
+        self.tgt = torch.as_tensor(tgt, device=dev)
+        self.tptr = torch.as_tensor(tptr, device=dev)
+        self.teid = torch.as_tensor(order.astype(np.int32), device=dev)
+        self.edge_attr = torch.as_tensor(np.ascontiguousarray(ea), device=dev)
+        self.x = torch.as_tensor(np.repeat((1.0 / sizes).astype(np.float32), sizes)[:, None],
+                                 device=dev)
+        self.edge_index = torch.stack([self.src.long(), self.tgt.long()])
+        self._gcn = None
+        self._shared = {"plan": None, "kptr": {}}  # shared by the copies with_* make
+
+    def _copy(self):
+        g = object.__new__(GraphBatch)
+        g.__dict__.update(self.__dict__)
+        return g
+
+    def with_clusters(self, col):
+        """Graph.with_clusters on the stack (col: aggregate column of every node, -1: none)."""
+        g = self._copy()
+        c = torch.where(col < 0, torch.zeros_like(col), col)
+        adj = (c[self.src.long()] != c[self.tgt.long()]).to(torch.float32)
+        g.edge_attr = torch.stack([self.edge_attr[:, 0], adj], dim=1).contiguous()
+        g.fe = 2
+        return g
+
+    def with_x(self, x):
+        """The stack with the node input x (n values, graph after graph) instead of 1/n_g."""
+        g = self._copy()
+        x = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x,
+                            dtype=torch.float32)
+        g.x = x.reshape(self.n, 1).to(self.device)
+        return g
+
+    csr = Graph.csr
+
+    def gcn_weights(self):
+        """Graph.gcn_weights on the stack (per node and per edge: the single graph's bits).
+        Edge feature 0 never changes, so the copies share the cached weights."""
+        if "gcn" not in self._shared:
+            self._shared["gcn"] = Graph.gcn_weights(self)
+        return self._shared["gcn"]
+
+    def k_ptr(self, alpha):
+        """Offsets of k_g = ceil(alpha n_g) seeds per graph (SegPtr), cached per alpha."""
+        key = float(alpha)
+        cache = self._shared["kptr"]
+        if key not in cache:
+            ks = [int(np.ceil(alpha * int(m))) for m in self.sizes]
+            cache[key] = SegPtr(np.concatenate([[0], np.cumsum(ks)]), self.device)
+        return cache[key]
+
+    def plan(self):
+        """The Bellman-Ford level plan of the stacked pattern (graph.BellmanFordSegPlan)."""
+        if self._shared["plan"] is None:
+            from .graph import BellmanFordSegPlan
+            pattern = self.csr(torch.zeros(self.E, dtype=torch.float32, device=self.device))
+            self._shared["plan"] = BellmanFordSegPlan(pattern, self.seg.host)
+        return self._shared["plan"]
+
+
 # ------------------------------------------------------------------------------------ kernels
 def linear(x, W, b=None, act=0, out=None, beta=0.0, residual=None):
     x = x.contiguous()
@@ -128,6 +256,33 @@ def topk_vec(x, k):
     call("mlamg_gnn_topk", ptr(s), int(s.numel()), int(k), ptr(vec), _p(idx if k else None),
          stream_ptr())
     return vec, idx
+
+
+def instance_norm_seg(x, seg, eps=1e-5):
+    """instance_norm on every segment of a stack (seg: SegPtr of node offsets) in one launch;
+    segment g is bitwise instance_norm(x[seg.host[g]:seg.host[g + 1]])."""
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    call("mlamg_gnn_instance_norm_seg", ptr(x), ptr(seg.dev), seg.host_ptr,
+         int(seg.host.size - 1), int(x.shape[1]), float(eps), ptr(y), stream_ptr())
+    return y
+
+
+def topk_vec_seg(x, seg, kptr):
+    """topk_vec on every segment of a stack: (vec, idx) with kptr.host[g + 1] - kptr.host[g]
+    ones in segment g and their node ids in the stack, best first, in
+    idx[kptr.host[g]:kptr.host[g + 1]]. Does not synchronise."""
+    s = x.reshape(-1).contiguous()
+    vec = torch.empty_like(s)
+    idx = torch.empty(max(int(kptr.host[-1]), 1), dtype=torch.int32, device=s.device)
+    call("mlamg_gnn_topk_seg", ptr(s), ptr(seg.dev), seg.host_ptr, ptr(kptr.dev), kptr.host_ptr,
+         int(seg.host.size - 1), ptr(vec), ptr(idx), stream_ptr())
+    return vec, idx[:int(kptr.host[-1])]
+
+
+def _inorm(g, x):
+    """InstanceNorm over the nodes of every graph in g (a Graph or a GraphBatch)."""
+    return instance_norm_seg(x, g.seg) if isinstance(g, GraphBatch) else instance_norm(x)
 
 
 # ------------------------------------------------------------------------------------ modules
@@ -240,12 +395,12 @@ class MPNN(nn.Module):
     def run(self, g):
         x = g.x
         ea = g.edge_attr
-        x = self.node_conv_in.run(g, instance_norm(x), ea, act=1, residual=x)
+        x = self.node_conv_in.run(g, _inorm(g, x), ea, act=1, residual=x)
         ea = self.edge_conv_in.run(g, x, ea, act=1, residual=ea)
         for i in range(self.num_internal_conv):
-            x = self.node_convs[i].run(g, instance_norm(x), ea, act=1, residual=x)
+            x = self.node_convs[i].run(g, _inorm(g, x), ea, act=1, residual=x)
             ea = self.edge_convs[i].run(g, x, ea, act=1, residual=ea)
-        x = self.node_conv_out.run(g, instance_norm(x), ea, act=1)
+        x = self.node_conv_out.run(g, _inorm(g, x), ea, act=1)
         ea = self.edge_conv_out.run(g, x, ea, act=1)
         return x, ea
 
@@ -276,7 +431,7 @@ class AggBinarizationLayer(nn.Module):
         if x.dim() == 1:
             x = x.unsqueeze(1)
         for i in range(self.num_conv):
-            x = instance_norm(x)
+            x = _inorm(g, x)
             x = self.ncs[i].run(g, x, act=1)        # relu(TAGConv(x))
             for lin in self.fcs[i]:
                 if isinstance(lin, nn.Linear):
@@ -285,6 +440,9 @@ class AggBinarizationLayer(nn.Module):
 
     @torch.no_grad()
     def run(self, g, x, k):
+        """k: the seed count of a Graph, the seed offsets (SegPtr) of a GraphBatch."""
+        if isinstance(g, GraphBatch):
+            return topk_vec_seg(self.run_raw(g, x), g.seg, k)[0]
         return topk_vec(self.run_raw(g, x), k)[0]
 
 
@@ -384,3 +542,98 @@ class FullAggNet(nn.Module):
                                            M.shape).coalesce()
 
         return to_t(Agg), to_t(P), to_t(C), top_k, node_scores
+
+    @torch.no_grad()
+    def forward_stack(self, batch, alpha, aggregation="pyamg", x=None):
+        """forward() on every graph of a GraphBatch at once, results still stacked: a dict with
+        Agg, P, C (DeviceCSR on stack rows; Agg and P on stacked aggregate columns), top_k (seed
+        node ids in the stack, ascending), node_scores, kptr (SegPtr: seed / column offsets per
+        graph) and failed (numpy bool per graph: some node reached by no seed; "parallel" never
+        fails). The steps are forward()'s, each one call on the stack; InstanceNorm, top-k and
+        pyamg's sweep run their segmented kernels, so every graph's part carries the bits of
+        its own forward(). Launches and host synchronisations do not depend on the batch size."""
+        from .graph import (aggregate_op_device, bellman_ford_device,
+                            bellman_ford_pyamg_seg_device, labels_to_columns)
+        if aggregation not in ("pyamg", "pyamg64", "parallel"):
+            raise ValueError("aggregation must be 'pyamg', 'pyamg64' or 'parallel', got "
+                             f"{aggregation!r}")
+        if not isinstance(batch, GraphBatch):
+            raise TypeError("forward_batch takes a GraphBatch")
+        g = batch if x is None else batch.with_x(x)
+        kptr = batch.k_ptr(alpha)
+        node_scores = self.AggNet.run(g, kptr).reshape(-1)
+        top_k = torch.nonzero(node_scores == 1).reshape(-1)  # k_g per graph, graph after graph
+        _, bf_edges = self.CNet.run(g)
+        C = g.csr(bf_edges)
+        seeds = top_k.to(torch.int32)
+        failed = np.zeros(batch.nb, dtype=bool)
+        if aggregation != "parallel":
+            _, lab, _ = bellman_ford_pyamg_seg_device(batch.plan(), C, seeds, kptr.host,
+                                                      fp64=aggregation == "pyamg64",
+                                                      seed_ptr_dev=kptr.dev)
+            lost = torch.zeros(batch.nb, dtype=torch.int32, device=lab.device)
+            lost.index_add_(0, batch.node_gid, (lab < 0).to(torch.int32))
+            failed = lost.cpu().numpy() > 0
+        else:
+            _, lab, _ = bellman_ford_device(C.T, seeds)
+        col = labels_to_columns(lab, seeds)
+        Agg = aggregate_op_device(col, int(kptr.host[-1]))
+        _, p_edges = self.PNet.run(g.with_clusters(col))
+        P = g.csr(p_edges) @ Agg
+        return dict(Agg=Agg, P=P, C=C, top_k=top_k, node_scores=node_scores, kptr=kptr,
+                    failed=failed)
+
+    @torch.no_grad()
+    def forward_batch(self, batch, alpha, aggregation="pyamg", x=None, strict=False):
+        """forward(A_g, alpha, aggregation) for every graph g of a GraphBatch, in a fixed
+        number of launches: a list with one entry per graph, the tuple forward() returns (local
+        indices, same dtypes, bitwise the same tensors) or None for a graph in which some node
+        is reached by no seed (forward() raises KeyError(-1) there; strict=True raises KeyError
+        naming the first such graph). The other graphs' results do not depend on a failed one.
+        k_g = ceil(alpha n_g). x: the per-node input hook of forward(), the graphs' inputs
+        concatenated. The sparse tensors of an entry are views into the stacked results."""
+        st = self.forward_stack(batch, alpha, aggregation, x)
+        failed, kptr = st["failed"], st["kptr"]
+        if strict and failed.any():
+            raise KeyError(f"graph {int(np.argmax(failed))} of the batch: a node is reached by "
+                           "no seed (-1)")
+        seg, gid = batch.seg, batch.node_gid
+        nrow = torch.arange(batch.n, device=gid.device)
+
+        def stacked(M, coff, sort=False):
+            """(crow, local COO indices [2, nnz], fp32 values) of a stacked DeviceCSR, rows in
+            order and (sort: the SpGEMM leaves scipy's column order) columns ascending, as
+            forward()'s coalesce() leaves them."""
+            crow, cj, v = M.to_torch()
+            rows = torch.repeat_interleave(nrow, (crow[1:] - crow[:-1]).long(),
+                                           output_size=M.nnz)
+            cj = cj.long()
+            if sort:
+                order = torch.argsort(rows * M.shape[1] + cj)  # unique keys: one order
+                cj, v = cj[order], v[order]
+            gr = gid[rows]
+            return crow, torch.stack([rows - seg.dev[gr], cj - coff[gr]]), v.to(torch.float32)
+
+        crow_a, idx_a, val_a = stacked(st["Agg"], kptr.dev)
+        crow_p, idx_p, val_p = stacked(st["P"], kptr.dev, sort=True)
+        _, idx_c, val_c = stacked(st["C"], seg.dev)
+        cuts = torch.stack([crow_a[seg.dev], crow_p[seg.dev]]).cpu().numpy()
+        top_k = st["top_k"]
+        top_local = top_k - seg.dev[gid[top_k]]
+
+        def coo(idx, val, a, b, shape):
+            return torch.sparse_coo_tensor(idx[:, a:b], val[a:b], shape, is_coalesced=True)
+
+        out = []
+        for i in range(batch.nb):
+            if failed[i]:
+                out.append(None)
+                continue
+            n = int(batch.sizes[i])
+            k0, k1 = int(kptr.host[i]), int(kptr.host[i + 1])
+            r0, e0, e1 = int(seg.host[i]), int(batch.eseg.host[i]), int(batch.eseg.host[i + 1])
+            out.append((coo(idx_a, val_a, int(cuts[0, i]), int(cuts[0, i + 1]), (n, k1 - k0)),
+                        coo(idx_p, val_p, int(cuts[1, i]), int(cuts[1, i + 1]), (n, k1 - k0)),
+                        coo(idx_c, val_c, e0, e1, (n, n)),
+                        top_local[k0:k1], st["node_scores"][r0:r0 + n]))
+        return out

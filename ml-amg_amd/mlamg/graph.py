@@ -84,6 +84,63 @@ def bellman_ford_pyamg_device(G, seeds_dev, fp64=False):
     return dist, near, int(sweeps.value)
 
 
+def _i64_host(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+class BellmanFordSegPlan:
+    """The level schedules of pyamg's pull sweep on a block-diagonal stack of graphs, one per
+    diagonal block (mlamg_bellman_ford_pyamg_seg_plan_create): built once from the pattern of G
+    (a DeviceCSR) and the node offsets seg_ptr (host int64[nb + 1]), reused for every weight
+    vector on that pattern."""
+
+    def __init__(self, G, seg_ptr):
+        self.seg_host = _i64_host(seg_ptr)
+        self.nb = int(self.seg_host.size - 1)
+        self.n = int(G.shape[0])
+        h = ctypes.c_void_p()
+        call("mlamg_bellman_ford_pyamg_seg_plan_create", G.handle, None,
+             self.seg_host.ctypes.data_as(ctypes.c_void_p), self.nb, ctypes.byref(h), stream_ptr())
+        self.handle = h
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                from . import _lib
+                _lib.lib.mlamg_bellman_ford_pyamg_seg_plan_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
+def bellman_ford_pyamg_seg_device(plan, G, seeds_dev, seed_ptr, fp64=False, seed_ptr_dev=None,
+                                  out=None):
+    """pyamg 4.x graph.bellman_ford on every graph of a block-diagonal stack at once, one
+    workgroup per graph. seeds_dev: int32 node ids in the stack, graph g's in
+    seeds_dev[seed_ptr[g]:seed_ptr[g + 1]] (seed_ptr: host int64[nb + 1]; seed_ptr_dev: the same
+    on the device if the caller has it). out: (dist, nearest) tensors to write into.
+
+    Returns (distances, nearest seed (node id in the stack, -1 unreached), sweeps per graph
+    (numpy int32[nb])): per graph bitwise bellman_ford_pyamg_device on that graph alone."""
+    dev = _device()
+    sp_h = _i64_host(seed_ptr)
+    if sp_h.size != plan.nb + 1:
+        raise ValueError(f"seed_ptr has {sp_h.size} entries for {plan.nb} graphs")
+    if seed_ptr_dev is None:
+        seed_ptr_dev = torch.as_tensor(sp_h).to(dev)
+    if out is None:
+        dist = torch.empty(plan.n, dtype=torch.float64 if fp64 else torch.float32, device=dev)
+        near = torch.empty(plan.n, dtype=torch.int32, device=dev)
+    else:
+        dist, near = out
+    sweeps = np.zeros(plan.nb, dtype=np.int32)
+    call("mlamg_bellman_ford_pyamg_seg", plan.handle, G.handle, ptr(seeds_dev), ptr(seed_ptr_dev),
+         sp_h.ctypes.data_as(ctypes.c_void_p), 1 if fp64 else 0, ptr(dist), ptr(near),
+         sweeps.ctypes.data_as(ctypes.c_void_p), stream_ptr())
+    return dist, near, sweeps
+
+
 def bellman_ford(G, seeds, maxiter=None):
     """Drop-in for pyamg.graph.bellman_ford (pyamg 4.x, as ns/model/agg_interp.py:475 calls it).
 
