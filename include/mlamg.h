@@ -255,7 +255,8 @@ int mlamg_gnn_gcn_norm(const int32_t* tptr, const int32_t* teid, const int32_t* 
 int mlamg_gnn_propagate(const int32_t* tptr, const int32_t* teid, const int32_t* src,
                         const float* w, const float* X, int64_t n, int F, float* Y, void* stream);
 /* torch_geometric InstanceNorm (affine False, no running stats): per channel over the nodes,
- * (x - mean) / sqrt(biased variance + eps). Limits: n >= 1, F >= 1 (no upper limit). */
+ * (x - mean) / sqrt(biased variance + eps). The kernel of mlamg_gnn_instance_norm_seg on the one
+ * segment [0, n). Limits: n >= 1, F >= 1 (no upper limit). */
 int mlamg_gnn_instance_norm(const float* X, int64_t n, int F, float eps, float* Y, void* stream);
 /* NNConv(Fin, Fout, nn = Linear(fe,4)-ReLU-Linear(4,16)-ReLU-Linear(16,Fin*Fout)-ReLU), aggr
  * 'add', root weight `root` = X W_root^T (precomputed), bias; msg_tmp[E*Fout] scratch (not
@@ -276,7 +277,9 @@ int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, i
                        void* stream);
 /* topk_vec (agg_interp.py:14-22): vec[n] = 1 at the k largest scores (ties, -0.0 == +0.0 among
  * them: smaller index first), idx[k] (nullable) = those nodes in that order; the order of NaN
- * scores is unspecified. Limits: 0 <= k <= n. Syncs. */
+ * scores is unspecified. mlamg_gnn_topk_seg's sort and kernels on one segment, out of the same
+ * cached per-thread block: no allocation after the first call of a size.
+ * Limits: 0 <= k <= n < 2^31 - 1 (int32 node ids). Syncs. */
 int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_t* idx,
                    void* stream);
 
@@ -286,19 +289,21 @@ int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_
  * (NULL: the entry copies the device array back, one synchronisation). The two must be equal.
  *
  * InstanceNorm per graph and channel: segment g of Y is bitwise mlamg_gnn_instance_norm on rows
- * seg_ptr[g] .. seg_ptr[g + 1] of X alone (the same strided double sums, wave sums and order of
- * the wave partials, one workgroup per (graph, channel)). Does not synchronise with the host
- * mirror given. Limits: every segment has >= 1 row, F >= 1 (EINVAL before any launch). */
+ * seg_ptr[g] .. seg_ptr[g + 1] of X alone (one kernel serves both: strided double sums, wave
+ * sums, the wave partials in order, one workgroup per (graph, channel)). Does not synchronise
+ * with the host mirror given. Limits: every segment has >= 1 row, F >= 1 (EINVAL before any
+ * launch). */
 int mlamg_gnn_instance_norm_seg(const float* X, const int64_t* seg_ptr,
                                 const int64_t* seg_ptr_host, int64_t nb, int F, float eps,
                                 float* Y, void* stream);
 /* topk_vec per graph: vec[n] = 1 at the k_g = k_ptr[g + 1] - k_ptr[g] largest scores of segment
  * g, 0 elsewhere; idx[k_ptr[g] .. k_ptr[g + 1]) = their node ids IN THE STACK, best first, in
  * the order of mlamg_gnn_topk (score descending under IEEE comparison, -0.0 == +0.0, then node
- * index ascending), so both are what mlamg_gnn_topk gives on the segment alone (idx + seg_ptr[g]).
- * One stable radix sort over the stack (key: segment id, then score); its storage comes from a
- * cached per-thread block, and with the host mirrors given the call neither allocates (after the
- * first of its size) nor synchronises. Limits: 0 <= k_g <= n_g (n_g = 0 allowed), the stack has
+ * index ascending), so both are what mlamg_gnn_topk gives on the segment alone (idx + seg_ptr[g]):
+ * that entry is this one on a single segment. One stable radix sort of (key, node index) pairs
+ * over the stack (key: segment id, then score); its storage comes from a cached per-thread block,
+ * and with the host mirrors given the call neither allocates (after the first of its size) nor
+ * synchronises. Limits: 0 <= k_g <= n_g (n_g = 0 allowed), the stack has
  * fewer than 2^31 - 1 rows; the order of NaN scores is unspecified. EINVAL before any launch. */
 int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_t* seg_ptr_host,
                        const int64_t* k_ptr, const int64_t* k_ptr_host, int64_t nb, float* vec,
@@ -359,7 +364,8 @@ int mlamg_bellman_ford_pyamg(const mlamg_csr* G, const int32_t* seeds, int32_t k
 /* The same sweep on a block-diagonal stack of nb graphs, one workgroup per graph: each walks the
  * level schedule of its own diagonal block and sweeps to its own fixed point, so per graph the
  * distances, the nearest seeds and the sweep count are bitwise mlamg_bellman_ford_pyamg on that
- * graph alone (nearest seeds as node ids in the stack).
+ * graph alone (nearest seeds as node ids in the stack). The two entries share the level rule,
+ * the level bucketing and the sweep loop (csrc/graph.hip); they differ in how they launch it.
  *
  * plan_create reads G's pattern once on the host (the only host pass; syncs) and keeps, per
  * graph, its rows in level order and its level pointers. seg_ptr as in mlamg_gnn_*_seg above

@@ -423,4 +423,37 @@ int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStr
 int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s);
 int dense_solve_mv(const mlamg_dense* D, const double* B, int64_t ldb, double* X, int64_t ldx,
                    int k, double* ytmp, hipStream_t s, const int32_t* done = nullptr);
+
+// Segment offsets of a stack (int64[nb + 1] from 0; gnn.hip, graph.hip). The segment g with
+// ptr[g] <= t < ptr[g + 1] (empty segments are skipped): the last g in [0, nb) with ptr[g] <= t.
+__device__ __forceinline__ int64_t seg_of(const int64_t* __restrict__ ptr, int64_t nb, int64_t t) {
+  int64_t lo = 0, hi = nb - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (ptr[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+// The offsets on the host: the caller's mirror, or a copy of the device array (one
+// synchronisation). Checks ptr[0] == 0 and that no step is below `min_step`.
+inline int host_ptr(const int64_t* dev, const int64_t* host, int64_t nb, int64_t min_step,
+                    hipStream_t s, std::vector<int64_t>& out, const char* what) {
+  out.assign((size_t)nb + 1, 0);
+  if (host) {
+    std::copy(host, host + nb + 1, out.begin());
+  } else {
+    MLAMG_HIP(hipMemcpyAsync(out.data(), dev, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost,
+                             s));
+    MLAMG_HIP(hipStreamSynchronize(s));
+  }
+  bool ok = out[0] == 0;
+  for (int64_t g = 0; g < nb; ++g) ok = ok && out[g + 1] - out[g] >= min_step;
+  if (!ok) {
+    set_error(std::string(what) + (min_step > 0 ? ": offsets must start at 0 and every segment "
+                                                  "needs at least one row"
+                                                : ": offsets must start at 0 and not decrease"));
+    return MLAMG_EINVAL;
+  }
+  return MLAMG_OK;
+}
 }  // namespace mlamg

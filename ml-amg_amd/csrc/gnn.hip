@@ -99,45 +99,20 @@ __global__ void k_gcn_weight(const int32_t* __restrict__ src, const int32_t* __r
   MLAMG_GRID_STRIDE(e, E, kT, threadIdx.x) wn[e] = (dis[src[e]] * w[e * wstride]) * dis[tgt[e]];
 }
 
-// instance norm over nodes, per channel (affine False, biased variance, eps): a block per channel
-__global__ void k_inorm(const float* __restrict__ X, int64_t n, int F, float eps,
-                        float* __restrict__ Y) {
-  __shared__ double red[kT / 64];
-  const int f = blockIdx.x;
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += kT) s += X[i * F + f];
-  s = wsum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = s;
-  __syncthreads();
-  double tot = 0.0;
-  for (int w = 0; w < kT / 64; ++w) tot += red[w];
-  const double mean = tot / (double)n;
-  __syncthreads();
-  double v = 0.0;
-  for (int64_t i = threadIdx.x; i < n; i += kT) {
-    const double d = X[i * F + f] - mean;
-    v += d * d;
-  }
-  v = wsum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = v;
-  __syncthreads();
-  double vt = 0.0;
-  for (int w = 0; w < kT / 64; ++w) vt += red[w];
-  const float inv = (float)(1.0 / sqrt(vt / (double)n + (double)eps));
-  const float mf = (float)mean;
-  for (int64_t i = threadIdx.x; i < n; i += kT) Y[i * F + f] = (X[i * F + f] - mf) * inv;
-}
-
-// the same over a stack of graphs: item = (segment g, channel f), a block per item; inside the
-// segment (rows seg[g] .. seg[g + 1]) the loop bodies, the wave sums and the order over the four
-// wave partials are k_inorm's on that segment alone, so the result is too, bit for bit
+// instance norm over the nodes of a segment, per channel (affine False, biased variance, eps):
+// item = (segment g, channel f), a block per item; rows seg[g] .. seg[g + 1] of the stack, or the
+// one segment [0, n) when seg is null. The sums run in double over the block's strided rows,
+// then the wave, then the four wave partials in order: a segment's result depends on its own
+// rows alone, wherever it sits in a stack.
 __global__ void k_inorm_seg(const float* __restrict__ Xs, const int64_t* __restrict__ seg,
-                            int64_t items, int F, float eps, float* __restrict__ Ys) {
+                            int64_t n_rows, int64_t items, int F, float eps,
+                            float* __restrict__ Ys) {
   __shared__ double red[kT / 64];
   MLAMG_GRID_STRIDE(it, items, 1, 0) {  // `it` is block-uniform: the block strides together
-    const int64_t g = it / F;
-    const int f = (int)(it % F);
-    const int64_t a = seg[g], n = seg[g + 1] - a;
+    // one segment: items = F, so the item is the channel (no 64-bit divide, no offset loads)
+    const int64_t g = seg ? it / F : 0;
+    const int f = seg ? (int)(it % F) : (int)it;
+    const int64_t a = seg ? seg[g] : 0, n = seg ? seg[g + 1] - a : n_rows;
     const float* X = Xs + a * F;
     float* Y = Ys + a * F;
     double s = 0.0;
@@ -285,88 +260,81 @@ __global__ void k_edge_mlp(const int32_t* __restrict__ src, const int32_t* __res
   }
 }
 
-// top-k: keys ordered by descending score (IEEE comparison: the two zeros are one score), then
-// ascending node index
-__global__ void k_topk_keys(const float* __restrict__ s, int64_t n, uint64_t* __restrict__ key) {
-  MLAMG_GRID_STRIDE(i, n, kT, threadIdx.x) {
-    uint32_t u = __float_as_uint(s[i]);
-    if ((u << 1) == 0u) u = 0u;  // -0.0 == +0.0 is a tie: the index decides, not the sign bit
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending order of the float
-    key[i] = ((uint64_t)(~u) << 32) | (uint64_t)i;
-  }
+// top-k. The key word of a score: ascending words = descending scores under IEEE comparison
+// (the two zeros are one score, so between them the node index decides, not the sign bit).
+__device__ __forceinline__ uint32_t topk_word(float s) {
+  uint32_t u = __float_as_uint(s);
+  if ((u << 1) == 0u) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending order of the float
+  return ~u;
 }
-__global__ void k_topk_mark(const uint64_t* __restrict__ key, int64_t k, float* __restrict__ vec,
-                            int32_t* __restrict__ idx) {
-  MLAMG_GRID_STRIDE(q, k, kT, threadIdx.x) {
-    const int32_t i = (int32_t)(key[q] & 0xffffffffu);
-    vec[i] = 1.0f;
-    if (idx) idx[q] = i;
-  }
-}
-
-// top-k per segment of a stack. The segment g with ptr[g] <= t < ptr[g + 1] (empty segments are
-// skipped): the last g in [0, nb) with ptr[g] <= t.
-__device__ __forceinline__ int64_t seg_of(const int64_t* __restrict__ ptr, int64_t nb, int64_t t) {
-  int64_t lo = 0, hi = nb - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (ptr[mid] <= t) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// key = segment id | k_topk_keys' descending-score word; the node index rides along as the
+// key = segment id | score word (seg null: one segment); the node index rides along as the
 // value. The radix sort is stable and the input is in ascending node order, so equal scores of a
-// segment stay in ascending index: the order of k_topk_keys inside every segment.
+// segment stay in ascending index.
 __global__ void k_topk_seg_keys(const float* __restrict__ s, const int64_t* __restrict__ seg,
                                 int64_t nb, int64_t n, uint64_t* __restrict__ key,
                                 int32_t* __restrict__ val) {
   MLAMG_GRID_STRIDE(i, n, kT, threadIdx.x) {
-    uint32_t u = __float_as_uint(s[i]);
-    if ((u << 1) == 0u) u = 0u;
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    key[i] = ((uint64_t)seg_of(seg, nb, i) << 32) | (uint64_t)(~u);
+    const uint64_t g = seg ? (uint64_t)seg_of(seg, nb, i) : 0;
+    key[i] = (g << 32) | (uint64_t)topk_word(s[i]);
     val[i] = (int32_t)i;
   }
 }
 // entry t of idx belongs to segment g = seg_of(kptr, t) and is that segment's (t - kptr[g])-th
-// best: position seg[g] + t - kptr[g] of the sorted stack
+// best: position seg[g] + t - kptr[g] of the sorted stack (kptr null: one segment from 0, so
+// position t). idx is nullable.
 __global__ void k_topk_seg_mark(const int32_t* __restrict__ sorted, const int64_t* __restrict__ seg,
                                 const int64_t* __restrict__ kptr, int64_t nb, int64_t K,
                                 float* __restrict__ vec, int32_t* __restrict__ idx) {
   MLAMG_GRID_STRIDE(t, K, kT, threadIdx.x) {
-    const int64_t g = seg_of(kptr, nb, t);
-    const int32_t i = sorted[seg[g] + (t - kptr[g])];
+    int64_t pos = t;
+    if (kptr) {
+      const int64_t g = seg_of(kptr, nb, t);
+      pos = seg[g] + (t - kptr[g]);
+    }
+    const int32_t i = sorted[pos];
     vec[i] = 1.0f;
-    idx[t] = i;
+    if (idx) idx[t] = i;
   }
-}
-
-// a segment pointer array on the host: the caller's mirror, or a copy of the device array (one
-// synchronisation). Checks ptr[0] == 0 and that no step is below `min_step`.
-int host_ptr(const int64_t* dev, const int64_t* host, int64_t nb, int64_t min_step, hipStream_t s,
-             std::vector<int64_t>& out, const char* what) {
-  out.assign((size_t)nb + 1, 0);
-  if (host) {
-    std::copy(host, host + nb + 1, out.begin());
-  } else {
-    MLAMG_HIP(hipMemcpyAsync(out.data(), dev, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
-    MLAMG_HIP(hipStreamSynchronize(s));
-  }
-  bool ok = out[0] == 0;
-  for (int64_t g = 0; g < nb; ++g) ok = ok && out[g + 1] - out[g] >= min_step;
-  if (!ok) {
-    set_error(std::string(what) + (min_step > 0 ? ": offsets must start at 0 and every segment "
-                                                  "needs at least one row"
-                                                : ": offsets must start at 0 and not decrease"));
-    return MLAMG_EINVAL;
-  }
-  return MLAMG_OK;
 }
 
 // The grid of a launch over n items, `per` to a block. The cap keeps the grid within HIP's limit
 // on threads per launch; MLAMG_GRID_STRIDE in every kernel covers the items beyond it.
 inline unsigned blocks(int64_t n, int per) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 1 << 20));
+}
+
+// top-k of every segment of a stack of n rows (seg_ptr / k_ptr null: one segment, its k = K):
+// one stable sort of (segment id | score word, node index) pairs over the bits in use, then the
+// K marks. Everything lives in one cached block: keys in | keys out | values in | values out |
+// the sort's own storage. Asynchronous on s.
+int topk_run(const float* scores, const int64_t* seg_ptr, const int64_t* k_ptr, int64_t nb,
+             int64_t n, int64_t K, float* vec, int32_t* idx, hipStream_t s) {
+  int seg_bits = 0;
+  while ((int64_t(1) << seg_bits) < nb) ++seg_bits;
+  size_t tb = 0;
+  MLAMG_HIP(rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr,
+                                      (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, 0,
+                                      32 + seg_bits, s));
+  const size_t kb = (sizeof(uint64_t) * (size_t)n + 255) / 256 * 256;
+  const size_t vb = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
+  char* base = static_cast<char*>(scratch(2 * kb + 2 * vb + tb + 256, 19));
+  MLAMG_REQUIRE(base, "topk: scratch allocation failed");
+  uint64_t* k0 = reinterpret_cast<uint64_t*>(base);
+  uint64_t* k1 = reinterpret_cast<uint64_t*>(base + kb);
+  int32_t* v0 = reinterpret_cast<int32_t*>(base + 2 * kb);
+  int32_t* v1 = reinterpret_cast<int32_t*>(base + 2 * kb + vb);
+  void* tmp = base + 2 * kb + 2 * vb;
+  hipLaunchKernelGGL(k_topk_seg_keys, dim3(blocks(n, kT)), dim3(kT), 0, s, scores, seg_ptr, nb, n,
+                     k0, v0);
+  MLAMG_HIP(hipGetLastError());
+  MLAMG_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, (size_t)n, 0, 32 + seg_bits, s));
+  MLAMG_HIP(hipMemsetAsync(vec, 0, sizeof(float) * n, s));
+  if (K > 0)
+    hipLaunchKernelGGL(k_topk_seg_mark, dim3(blocks(K, kT)), dim3(kT), 0, s, v1, seg_ptr, k_ptr, nb,
+                       K, vec, idx);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
 }
 
 }  // namespace
@@ -416,7 +384,8 @@ int mlamg_gnn_propagate(const int32_t* tptr, const int32_t* teid, const int32_t*
 
 int mlamg_gnn_instance_norm(const float* X, int64_t n, int F, float eps, float* Y, void* stream) {
   MLAMG_REQUIRE(n >= 1 && F >= 1, "instance norm: empty input");
-  hipLaunchKernelGGL(k_inorm, dim3(F), dim3(kT), 0, S(stream), X, n, F, eps, Y);
+  hipLaunchKernelGGL(k_inorm_seg, dim3(blocks(F, 1)), dim3(kT), 0, S(stream), X,
+                     (const int64_t*)nullptr, n, (int64_t)F, F, eps, Y);
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;
 }
@@ -431,9 +400,20 @@ int mlamg_gnn_instance_norm_seg(const float* X, const int64_t* seg_ptr,
   std::vector<int64_t> seg;
   MLAMG_TRY(host_ptr(seg_ptr, seg_ptr_host, nb, 1, S(stream), seg, "instance norm (segmented)"));
   const int64_t items = nb * (int64_t)F;
-  hipLaunchKernelGGL(k_inorm_seg, dim3(blocks(items, 1)), dim3(kT), 0, S(stream), X, seg_ptr,
-                     items, F, eps, Y);
+  // one segment: its bounds are known here, so the kernel does not read the offsets
+  hipLaunchKernelGGL(k_inorm_seg, dim3(blocks(items, 1)), dim3(kT), 0, S(stream), X,
+                     nb == 1 ? nullptr : seg_ptr, seg[nb], items, F, eps, Y);
   MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_t* idx,
+                   void* stream) {
+  MLAMG_REQUIRE(scores && vec && k >= 0 && k <= n, "topk: bad arguments");
+  MLAMG_REQUIRE(n < INT32_MAX, "topk: too many scores for int32 node ids");
+  hipStream_t s = S(stream);
+  if (n > 0) MLAMG_TRY(topk_run(scores, nullptr, nullptr, 1, n, k, vec, idx, s));
+  MLAMG_HIP(hipStreamSynchronize(s));
   return MLAMG_OK;
 }
 
@@ -454,32 +434,8 @@ int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_
   MLAMG_REQUIRE(n < INT32_MAX, "topk (segmented): stack too large for int32 node ids");
   if (n == 0) return MLAMG_OK;
   MLAMG_REQUIRE(scores && vec && (K == 0 || idx), "topk (segmented): NULL argument");
-  int seg_bits = 0;
-  while ((int64_t(1) << seg_bits) < nb) ++seg_bits;
-  // one cached block: keys in | keys out | values in | values out | the sort's own storage
-  size_t tb = 0;
-  MLAMG_HIP(rocprim::radix_sort_pairs(nullptr, tb, (uint64_t*)nullptr, (uint64_t*)nullptr,
-                                      (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, 0,
-                                      32 + seg_bits, s));
-  const size_t kb = (sizeof(uint64_t) * (size_t)n + 255) / 256 * 256;
-  const size_t vb = (sizeof(int32_t) * (size_t)n + 255) / 256 * 256;
-  char* base = static_cast<char*>(scratch(2 * kb + 2 * vb + tb + 256, 19));
-  MLAMG_REQUIRE(base, "topk (segmented): scratch allocation failed");
-  uint64_t* k0 = reinterpret_cast<uint64_t*>(base);
-  uint64_t* k1 = reinterpret_cast<uint64_t*>(base + kb);
-  int32_t* v0 = reinterpret_cast<int32_t*>(base + 2 * kb);
-  int32_t* v1 = reinterpret_cast<int32_t*>(base + 2 * kb + vb);
-  void* tmp = base + 2 * kb + 2 * vb;
-  hipLaunchKernelGGL(k_topk_seg_keys, dim3(blocks(n, kT)), dim3(kT), 0, s, scores, seg_ptr, nb, n,
-                     k0, v0);
-  MLAMG_HIP(hipGetLastError());
-  MLAMG_HIP(rocprim::radix_sort_pairs(tmp, tb, k0, k1, v0, v1, (size_t)n, 0, 32 + seg_bits, s));
-  MLAMG_HIP(hipMemsetAsync(vec, 0, sizeof(float) * n, s));
-  if (K > 0)
-    hipLaunchKernelGGL(k_topk_seg_mark, dim3(blocks(K, kT)), dim3(kT), 0, s, v1, seg_ptr, k_ptr, nb,
-                       K, vec, idx);
-  MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
+  if (nb == 1) return topk_run(scores, nullptr, nullptr, 1, n, K, vec, idx, s);  // as above
+  return topk_run(scores, seg_ptr, k_ptr, nb, n, K, vec, idx, s);
 }
 
 int mlamg_gnn_nnconv(const int32_t* tptr, const int32_t* teid, const int32_t* src,
@@ -511,35 +467,6 @@ int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, i
                      sizeof(float) * (2 * F + fe) * H, S(stream), src, tgt, X, F, ea, fe, E, W1,
                      b1, H, g, beta, W2, b2, C, act, R, rc, out);
   MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
-}
-
-int mlamg_gnn_topk(const float* scores, int64_t n, int64_t k, float* vec, int32_t* idx,
-                   void* stream) {
-  MLAMG_REQUIRE(scores && vec && k >= 0 && k <= n, "topk: bad arguments");
-  hipStream_t s = S(stream);
-  uint64_t *k0 = nullptr, *k1 = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0;
-  MLAMG_HIP(hipMalloc(&k0, sizeof(uint64_t) * std::max<int64_t>(n, 1)));
-  hipError_t e = hipMalloc(&k1, sizeof(uint64_t) * std::max<int64_t>(n, 1));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_topk_keys, dim3(blocks(n, kT)), dim3(kT), 0, s, scores, n, k0);
-    e = rocprim::radix_sort_keys(nullptr, tb, k0, k1, (size_t)n, 0, 64, s);
-  }
-  if (e == hipSuccess) e = hipMalloc(&tmp, std::max<size_t>(tb, 1));
-  if (e == hipSuccess) e = rocprim::radix_sort_keys(tmp, tb, k0, k1, (size_t)n, 0, 64, s);
-  if (e == hipSuccess) e = hipMemsetAsync(vec, 0, sizeof(float) * n, s);
-  if (e == hipSuccess && k > 0)
-    hipLaunchKernelGGL(k_topk_mark, dim3(blocks(k, kT)), dim3(kT), 0, s, k1, k, vec, idx);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(tmp);
-  (void)hipFree(k1);
-  (void)hipFree(k0);
-  if (e != hipSuccess) {
-    set_error(std::string("topk: ") + hipGetErrorString(e));
-    return MLAMG_EHIP;
-  }
   return MLAMG_OK;
 }
 

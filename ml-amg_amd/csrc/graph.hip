@@ -300,14 +300,17 @@ __device__ inline int pull_row(int32_t i, const int32_t* __restrict__ ip,
   return xi != x0;  // pyamg: (old_distances == distances).all()
 }
 
+// One workgroup sweeps the levels lptr[0 .. n_levels] (positions into `rows`) until a sweep
+// changes no distance, at most max_sweeps times. Every thread returns the sweep count and, in
+// *unconverged, whether the last sweep still changed something; the last barrier is behind every
+// write to x and z. lptr is not __restrict__ on purpose: with it the compiler carries
+// lptr[l + 1] into the next level instead of loading the pair, and k_bf_pyamg_seg with x and z in
+// LDS measured 4 % slower.
 template <typename T>
-__global__ __launch_bounds__(kBfBlock) void k_bf_pyamg(const int32_t* __restrict__ ip,
-                                                       const int32_t* __restrict__ ij,
-                                                       const double* __restrict__ ax,
-                                                       const int32_t* __restrict__ rows,
-                                                       const int32_t* __restrict__ lptr,
-                                                       int32_t n_levels, int32_t max_sweeps, T* x,
-                                                       int32_t* z, int32_t* __restrict__ out) {
+__device__ __forceinline__ int32_t pull_to_fixed_point(
+    const int32_t* __restrict__ ip, const int32_t* __restrict__ ij, const double* __restrict__ ax,
+    const int32_t* __restrict__ rows, const int32_t* lptr, int32_t n_levels, int32_t max_sweeps,
+    T* x, int32_t* z, int32_t* unconverged) {
   __shared__ int32_t changed;
   int32_t sweeps = 0, c = 0;
   do {
@@ -326,6 +329,22 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_pyamg(const int32_t* __restrict
     c = changed;
     __syncthreads();  // every thread has read the flag before it is reset
   } while (c && sweeps < max_sweeps);
+  *unconverged = c;
+  return sweeps;
+}
+
+// on (x, z) as they stand: a seeded start (mlamg_bellman_ford_pyamg) or Lloyd's (d, c)
+template <typename T>
+__global__ __launch_bounds__(kBfBlock) void k_bf_pyamg(const int32_t* __restrict__ ip,
+                                                       const int32_t* __restrict__ ij,
+                                                       const double* __restrict__ ax,
+                                                       const int32_t* __restrict__ rows,
+                                                       const int32_t* __restrict__ lptr,
+                                                       int32_t n_levels, int32_t max_sweeps, T* x,
+                                                       int32_t* z, int32_t* __restrict__ out) {
+  int32_t c = 0;
+  const int32_t sweeps = pull_to_fixed_point<T>(ip, ij, ax, rows, lptr, n_levels, max_sweeps, x, z,
+                                                &c);
   if (threadIdx.x == 0) {
     out[0] = sweeps;
     out[1] = c;
@@ -334,7 +353,7 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_pyamg(const int32_t* __restrict
 
 // The same on a block-diagonal stack: workgroup g owns rows seg[g] .. seg[g + 1], its seeds
 // seeds[sptr[g] .. sptr[g + 1]) and levels lptr[loff[g] .. loff[g + 1]) (positions into `rows`).
-// It initialises, seeds and sweeps its own block to its own fixed point with k_bf_pyamg's loop;
+// It initialises, seeds and sweeps its own block to its own fixed point (pull_to_fixed_point);
 // pull_row reads only the block's own x and z (G is block diagonal), so every (x, z) and the
 // sweep count are the single graph's. out[2 g] = sweeps, out[2 g + 1] = unconverged. *bad (set by
 // k_bf_seg_check_seeds) makes every workgroup leave before it writes anything.
@@ -347,7 +366,6 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_pyamg_seg(
     const int32_t* __restrict__ lptr, const int32_t* __restrict__ rows,
     const int32_t* __restrict__ seeds, const int64_t* __restrict__ sptr, T big, T* xg, int32_t* zg,
     int32_t cap, const int32_t* __restrict__ bad, int32_t* __restrict__ out) {
-  __shared__ int32_t changed;
   extern __shared__ double bf_lds[];  // LDS: x[cap] | z[cap]
   if (*bad) return;  // the same word for every thread: the block leaves as one
   const int32_t g = blockIdx.x;
@@ -366,27 +384,10 @@ __global__ __launch_bounds__(kBfBlock) void k_bf_pyamg_seg(
     z[sd] = sd;
   }
   __syncthreads();
-  const int32_t* lp = lptr + loff[g];
-  const int32_t n_levels = loff[g + 1] - loff[g] - 1;
-  const int32_t max_sweeps = r1 - r0 + 2;
-  int32_t sweeps = 0, c = 0;
-  do {
-    if (threadIdx.x == 0) changed = 0;
-    __syncthreads();
-    int any = 0;
-    for (int32_t l = 0; l < n_levels; ++l) {
-      const int32_t a = lp[l], e = lp[l + 1];
-      for (int32_t t = a + (int32_t)threadIdx.x; t < e; t += kBfBlock)
-        any |= pull_row<T>(rows[t], ip, ij, ax, x, z);
-      __syncthreads();
-    }
-    if (any) changed = 1;
-    __syncthreads();
-    ++sweeps;
-    c = changed;
-    __syncthreads();
-  } while (c && sweeps < max_sweeps);
-  if (LDS)  // the loop's last barrier is behind every write
+  int32_t c = 0;
+  const int32_t sweeps = pull_to_fixed_point<T>(ip, ij, ax, rows, lptr + loff[g],
+                                                loff[g + 1] - loff[g] - 1, r1 - r0 + 2, x, z, &c);
+  if (LDS)  // the sweeps' last barrier is behind every write
     for (int32_t i = r0 + (int32_t)threadIdx.x; i < r1; i += kBfBlock) {
       xg[i] = x[i];
       zg[i] = z[i];
@@ -403,13 +404,9 @@ __global__ void k_bf_seg_check_seeds(const int32_t* __restrict__ seeds,
                                      const int32_t* __restrict__ seg, int32_t nb, int64_t K,
                                      int32_t* __restrict__ bad) {
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < K; t += (int64_t)gridDim.x * 256) {
-    int32_t lo = 0, hi = nb - 1;
-    while (lo < hi) {
-      const int32_t mid = (lo + hi + 1) >> 1;
-      if (sptr[mid] <= t) lo = mid; else hi = mid - 1;
-    }
+    const int64_t g = seg_of(sptr, nb, t);
     const int32_t sd = seeds[t];
-    if (sd < seg[lo] || sd >= seg[lo + 1]) *bad = 1;
+    if (sd < seg[g] || sd >= seg[g + 1]) *bad = 1;
   }
 }
 
@@ -550,35 +547,58 @@ static int fetch_pattern(const mlamg_csr* G, hipStream_t s, std::vector<int32_t>
   return MLAMG_OK;
 }
 
-// rows bucketed by level; extra = trailing int32 words reserved after rows | out
+// rows [a, b) bucketed by level into the zeroed lp[nlev + 1] and `rows` (indexed from row 0):
+// level l's rows, ascending, are rows[lp[l] .. lp[l + 1]), lp[0] = a
+static void bucket_levels(const int32_t* level, int64_t a, int64_t b, int32_t nlev, int32_t* lp,
+                          int32_t* rows) {
+  for (int64_t i = a; i < b; ++i) lp[level[i] + 1]++;
+  lp[0] = (int32_t)a;
+  for (int32_t l = 0; l < nlev; ++l) lp[l + 1] += lp[l];
+  std::vector<int32_t> fill(lp, lp + nlev);
+  for (int64_t i = a; i < b; ++i) rows[fill[level[i]]++] = (int32_t)i;
+}
+
+// lptr | rows | out of all n rows; extra = trailing int32 words reserved after them
 static void plan_levels(const std::vector<int32_t>& level, int32_t nlev, size_t extra,
                         std::vector<int32_t>& plan) {
   const int64_t n = (int64_t)level.size();
   plan.assign((size_t)nlev + 1 + n + 2 + extra, 0);
-  int32_t* lp = plan.data();
-  for (int64_t i = 0; i < n; ++i) lp[level[i] + 1]++;
-  for (int32_t l = 0; l < nlev; ++l) lp[l + 1] += lp[l];
-  std::vector<int32_t> fill(lp, lp + nlev);
-  int32_t* rows = lp + nlev + 1;
-  for (int64_t i = 0; i < n; ++i) rows[fill[level[i]]++] = (int32_t)i;
+  bucket_levels(level.data(), 0, n, nlev, plan.data(), plan.data() + nlev + 1);
 }
 
-// pull sweep (pyamg): level(i) = 1 + max level(j) over j < i coupled either way
-static int build_pull_plan(const mlamg_csr* G, hipStream_t s, SeqPlan& P) {
-  const int64_t n = G->n_rows;
-  std::vector<int32_t> ip, ij;
-  MLAMG_TRY(fetch_pattern(G, s, ip, ij, nullptr));
-  std::vector<int32_t> level(n, 0), req(n, 0);
-  int32_t nlev = n ? 1 : 0;
-  for (int64_t i = 0; i < n; ++i) {
+// pull sweep (pyamg) on rows [a, b) of a pattern: level(i) = 1 + max level(j) over j < i
+// coupled either way (level and req: n zeros on entry). Returns the number of levels, or -1
+// with *out_row / *out_col set at the first entry that leaves [a, b) (out_row null: not checked).
+static int32_t pull_levels(const std::vector<int32_t>& ip, const std::vector<int32_t>& ij,
+                           int64_t a, int64_t b, std::vector<int32_t>& level,
+                           std::vector<int32_t>& req, int64_t* out_row = nullptr,
+                           int64_t* out_col = nullptr) {
+  int32_t nlev = 0;
+  for (int64_t i = a; i < b; ++i) {
     int32_t L = req[i];
-    for (int32_t q = ip[i]; q < ip[i + 1]; ++q)
-      if (ij[q] < i) L = std::max(L, level[ij[q]] + 1);
+    for (int32_t q = ip[i]; q < ip[i + 1]; ++q) {
+      const int64_t j = ij[q];
+      if (out_row && (j < a || j >= b)) {
+        *out_row = i;
+        *out_col = j;
+        return -1;
+      }
+      if (j < i) L = std::max(L, level[j] + 1);
+    }
     level[i] = L;
     for (int32_t q = ip[i]; q < ip[i + 1]; ++q)
       if (ij[q] > i) req[ij[q]] = std::max(req[ij[q]], L + 1);
     nlev = std::max(nlev, L + 1);
   }
+  return nlev;
+}
+
+static int build_pull_plan(const mlamg_csr* G, hipStream_t s, SeqPlan& P) {
+  const int64_t n = G->n_rows;
+  std::vector<int32_t> ip, ij;
+  MLAMG_TRY(fetch_pattern(G, s, ip, ij, nullptr));
+  std::vector<int32_t> level(n, 0), req(n, 0);
+  const int32_t nlev = pull_levels(ip, ij, 0, n, level, req);
   std::vector<int32_t> plan;
   plan_levels(level, nlev, 0, plan);
   P.n = n;
@@ -957,16 +977,10 @@ int mlamg_bellman_ford_pyamg_seg_plan_create(const mlamg_csr* G, const int64_t* 
   MLAMG_REQUIRE(nb < INT32_MAX, "too many graphs");
   hipStream_t s = S(stream);
   const int64_t n = G->n_rows;
-  std::vector<int64_t> seg((size_t)nb + 1, 0);
-  if (seg_ptr_host) {
-    std::copy(seg_ptr_host, seg_ptr_host + nb + 1, seg.begin());
-  } else {
-    MLAMG_HIP(hipMemcpyAsync(seg.data(), seg_ptr, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
-    MLAMG_HIP(hipStreamSynchronize(s));
-  }
-  MLAMG_REQUIRE(seg[0] == 0 && seg[nb] == n, "seg_ptr must run from 0 to the number of rows");
+  std::vector<int64_t> seg;
+  MLAMG_TRY(host_ptr(seg_ptr, seg_ptr_host, nb, 0, s, seg, "bellman_ford_pyamg_seg seg_ptr"));
+  MLAMG_REQUIRE(seg[nb] == n, "seg_ptr must end at the number of rows");
   for (int64_t g = 0; g < nb; ++g) {
-    MLAMG_REQUIRE(seg[g + 1] >= seg[g], "seg_ptr must not decrease");
     if (seg[g + 1] - seg[g] > kSeqOneBlockMax) {
       set_error("bellman_ford_pyamg_seg: graph " + std::to_string(g) + " has " +
                 std::to_string(seg[g + 1] - seg[g]) + " rows, above the one-workgroup limit " +
@@ -976,25 +990,16 @@ int mlamg_bellman_ford_pyamg_seg_plan_create(const mlamg_csr* G, const int64_t* 
   }
   std::vector<int32_t> ip, ij;
   MLAMG_TRY(fetch_pattern(G, s, ip, ij, nullptr));
-  // build_pull_plan's rule; a block-diagonal pattern couples a row only to rows of its own
-  // graph, so the levels of a block are those of the graph alone
+  // a block-diagonal pattern couples a row only to rows of its own graph, so the levels of a
+  // block are those of the graph alone
   std::vector<int32_t> level(n, 0), req(n, 0), nlev((size_t)nb, 0);
   for (int64_t g = 0; g < nb; ++g) {
-    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) {
-      int32_t L = req[i];
-      for (int32_t q = ip[i]; q < ip[i + 1]; ++q) {
-        const int64_t j = ij[q];
-        if (j < seg[g] || j >= seg[g + 1]) {
-          set_error("bellman_ford_pyamg_seg: not block diagonal: row " + std::to_string(i) +
-                    " of graph " + std::to_string(g) + " is coupled to column " + std::to_string(j));
-          return MLAMG_EINVAL;
-        }
-        if (j < i) L = std::max(L, level[j] + 1);
-      }
-      level[i] = L;
-      for (int32_t q = ip[i]; q < ip[i + 1]; ++q)
-        if (ij[q] > i) req[ij[q]] = std::max(req[ij[q]], L + 1);
-      nlev[g] = std::max(nlev[g], L + 1);
+    int64_t i = 0, j = 0;
+    nlev[g] = pull_levels(ip, ij, seg[g], seg[g + 1], level, req, &i, &j);
+    if (nlev[g] < 0) {
+      set_error("bellman_ford_pyamg_seg: not block diagonal: row " + std::to_string(i) +
+                " of graph " + std::to_string(g) + " is coupled to column " + std::to_string(j));
+      return MLAMG_EINVAL;
     }
   }
   // seg[nb + 1] | loff[nb + 1] | lptr[sum (nlev_g + 1)] | rows[n] | out[2 nb] | bad[1]
@@ -1007,14 +1012,9 @@ int mlamg_bellman_ford_pyamg_seg_plan_create(const mlamg_csr* G, const int64_t* 
     plan[g] = (int32_t)seg[g];
     plan[o_loff + g] = loff[g];
   }
-  for (int64_t g = 0; g < nb; ++g) {
-    int32_t* lp = plan.data() + o_lptr + loff[g];  // counts, then positions into rows
-    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) lp[level[i] + 1]++;
-    lp[0] = (int32_t)seg[g];
-    for (int32_t l = 0; l < nlev[g]; ++l) lp[l + 1] += lp[l];
-    std::vector<int32_t> fill(lp, lp + nlev[g]);
-    for (int64_t i = seg[g]; i < seg[g + 1]; ++i) plan[o_rows + fill[level[i]]++] = (int32_t)i;
-  }
+  for (int64_t g = 0; g < nb; ++g)
+    bucket_levels(level.data(), seg[g], seg[g + 1], nlev[g], plan.data() + o_lptr + loff[g],
+                  plan.data() + o_rows);
   auto* P = new mlamg_bf_seg_plan();
   P->n = n;
   P->nnz = G->nnz;
@@ -1053,15 +1053,8 @@ int mlamg_bellman_ford_pyamg_seg(const mlamg_bf_seg_plan* P, const mlamg_csr* G,
                 "bellman_ford_pyamg_seg: G does not have the plan's pattern");
   hipStream_t s = S(stream);
   const int64_t nb = P->nb;
-  std::vector<int64_t> sp((size_t)nb + 1, 0);
-  if (seed_ptr_host) {
-    std::copy(seed_ptr_host, seed_ptr_host + nb + 1, sp.begin());
-  } else {
-    MLAMG_HIP(hipMemcpyAsync(sp.data(), seed_ptr, sizeof(int64_t) * (nb + 1), hipMemcpyDeviceToHost, s));
-    MLAMG_HIP(hipStreamSynchronize(s));
-  }
-  MLAMG_REQUIRE(sp[0] == 0, "seed_ptr must start at 0");
-  for (int64_t g = 0; g < nb; ++g) MLAMG_REQUIRE(sp[g + 1] >= sp[g], "seed_ptr must not decrease");
+  std::vector<int64_t> sp;
+  MLAMG_TRY(host_ptr(seed_ptr, seed_ptr_host, nb, 0, s, sp, "bellman_ford_pyamg_seg seed_ptr"));
   const int64_t K = sp[nb];
   MLAMG_REQUIRE((P->n == 0 || (dist && nearest)) && (K == 0 || seeds), "NULL argument");
   int32_t* out = P->d + P->o_out;

@@ -11,13 +11,15 @@ not on torch ops. torch_geometric is absent: its layers (TAGConv K=3 with gcn_no
 trained weights are not shipped, so parity is against oracle/gnn_ref.py (a torch restatement
 of the same layers) at seeded weights — parity unpinned with respect to torch_geometric itself.
 
-`GraphBatch` + `FullAggNet.forward_batch` run the same forward pass on many graphs at once (the
-graphs stacked block-diagonally, the per-graph steps as segmented kernels), every graph's
-tensors bitwise its own `forward`.
+There is one forward pass, `FullAggNet.forward_stack`, on a `GraphBatch`: many graphs stacked
+block-diagonally, the per-graph steps (InstanceNorm, top-k, pyamg's sweep) done segment by
+segment. A `Graph` is a batch of one, `forward` runs it on that, `forward_batch` on many graphs at
+once, every graph's tensors bitwise its own `forward`.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import scipy.sparse as sp
@@ -33,107 +35,60 @@ def _p(t):
 
 
 # ------------------------------------------------------------------------------------ graphs
-class Graph:
-    """graph_from_matrix_basic(A) / graph_from_matrix(A, agg) (ns/model/data.py:22-46) on the
-    device: edges = A's stored entries in row-major order (networkx DiGraph order), edge_attr =
-    |a_ij| (fp32) [, cluster_adj = 0 if both ends are in the same aggregate], x = 1/n."""
-
-    def __init__(self, A, agg=None, device=None):
-        A = sp.csr_matrix(A)
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        n = A.shape[0]
-        src = np.repeat(np.arange(n, dtype=np.int32), np.diff(A.indptr))
-        tgt = A.indices.astype(np.int32)
-        feats = [np.abs(A.data.astype(np.float32))]
-        if agg is not None:
-            clusters = np.asarray(sp.csr_matrix(agg).argmax(axis=1)).ravel()
-            feats.append((clusters[src] != clusters[tgt]).astype(np.float32))
-        ea = np.stack(feats, axis=1)
-        order = np.argsort(tgt, kind="stable")          # each target's edges, ascending source
-        tptr = np.zeros(n + 1, dtype=np.int32)
-        np.cumsum(np.bincount(tgt, minlength=n), out=tptr[1:])
-        self.n, self.E, self.fe = n, int(len(src)), ea.shape[1]
-        self.crow = torch.as_tensor(A.indptr.astype(np.int32), device=dev)
-        self.src = torch.as_tensor(src, device=dev)
-        self.tgt = torch.as_tensor(tgt, device=dev)
-        self.tptr = torch.as_tensor(tptr, device=dev)
-        self.teid = torch.as_tensor(order.astype(np.int32), device=dev)
-        self.edge_attr = torch.as_tensor(np.ascontiguousarray(ea), device=dev)
-        self.x = torch.full((n, 1), 1.0 / n, dtype=torch.float32, device=dev)
-        self.edge_index = torch.stack([self.src.long(), self.tgt.long()])
-        self._gcn = None
-
-    def with_clusters(self, col):
-        """graph_from_matrix(A, Agg) from this graph and the device aggregate column of every
-        node (-1: none; agg_op.argmax(axis=1) of an empty row is 0): edge feature 2 =
-        cluster_adj = 0 if both ends are in the same aggregate, else 1. Shares the structure."""
-        g = object.__new__(Graph)
-        g.__dict__.update(self.__dict__)
-        c = torch.where(col < 0, torch.zeros_like(col), col)
-        adj = (c[self.src.long()] != c[self.tgt.long()]).to(torch.float32)
-        g.edge_attr = torch.stack([self.edge_attr[:, 0], adj], dim=1).contiguous()
-        g.fe = 2
-        g._gcn = None
-        return g
-
-    def csr(self, values):
-        """A DeviceCSR on this graph's pattern with the given per-edge values (fp64 copy)."""
-        from .sparse import DeviceCSR
-        return DeviceCSR.from_torch(self.crow, self.tgt, values.reshape(-1).double().contiguous(),
-                                    (self.n, self.n))
-
-    def gcn_weights(self):
-        """gcn_norm(edge_index, edge_attr[:, 0]) without self loops (TAGConv normalize=True)."""
-        if self._gcn is None:
-            w = self.edge_attr[:, 0].contiguous()
-            dis = torch.empty(self.n, dtype=torch.float32, device=w.device)
-            wn = torch.empty(self.E, dtype=torch.float32, device=w.device)
-            call("mlamg_gnn_gcn_norm", ptr(self.tptr), ptr(self.teid), ptr(self.src),
-                 ptr(self.tgt), ptr(w), int(self.n), int(self.E), ptr(dis), ptr(wn), stream_ptr())
-            self._gcn = wn
-        return self._gcn
+@functools.lru_cache(maxsize=1024)
+def _offsets_on_device(raw, device):
+    """int64 offsets (their bytes) as a read-only device tensor. forward() builds a Graph per
+    call, so the same few small arrays recur: each is uploaded once."""
+    return torch.as_tensor(np.frombuffer(raw, dtype=np.int64).copy()).to(device)
 
 
 class SegPtr:
     """Segment offsets of a stack, int64[nb + 1] from 0: on the host and on the device (the C
-    entry points validate the host copy, the kernels read the device copy)."""
+    entry points validate the host copy, the kernels read the device copy, made on first use)."""
 
     def __init__(self, host, device):
         self.host = np.ascontiguousarray(host, dtype=np.int64)
-        self.dev = torch.as_tensor(self.host).to(device)
+        self.device = torch.device(device)
+        self.nb = int(self.host.size - 1)
+        # made once: the layers pass it on every call, and numpy builds .ctypes anew each time
+        self.host_ptr = self.host.ctypes.data_as(ctypes.c_void_p)
 
-    @property
-    def host_ptr(self):
-        return self.host.ctypes.data_as(ctypes.c_void_p)
+    @functools.cached_property
+    def dev(self):
+        return _offsets_on_device(self.host.tobytes(), self.device)
 
 
 class GraphBatch:
-    """Many graphs as one block-diagonal stack, built once per dataset: the fields of
-    Graph(scipy.sparse.block_diag(As)) — node ids of graph g offset by seg.host[g], edges in
-    graph order — except x, which carries 1/n_g on graph g's nodes, plus the node and edge
-    segment pointers (seg, eseg), every node's graph id (node_gid), the cached gcn_norm weights
-    and the cached Bellman-Ford level plan (created on first use, on the device).
+    """Many graphs as one block-diagonal stack, built once per dataset. Per graph the fields are
+    graph_from_matrix_basic(A_g) (ns/model/data.py:22-31): edges = A_g's stored entries in
+    row-major order (networkx DiGraph order), edge_attr = |a_ij| (fp32), x = 1/n_g. On the stack
+    the node ids of graph g are offset by seg.host[g] and the edges follow in graph order — the
+    layout of scipy.sparse.block_diag(As) — with the node and edge segment pointers (seg, eseg),
+    every node's graph id (node_gid), the cached gcn_norm weights and the cached Bellman-Ford
+    level plan (created on first use, on the device).
 
     Every GNN kernel but InstanceNorm and top-k produces a row or an edge from its own inputs in
-    an order that does not depend on where the item sits, so on this stack it gives the bits of
-    the single call; the two exceptions and pyamg's sequential sweep have segmented kernels
-    (FullAggNet.forward_batch). Every matrix must have canonical format (sorted, duplicate-free
-    rows): pyamg would sweep a re-sorted, duplicate-summed copy, which stays with forward()."""
+    an order that does not depend on where the item sits; those two and pyamg's sequential sweep
+    work segment by segment. So every graph's part of a result carries the bits it has when the
+    graph runs alone. Every matrix must have canonical format (sorted, duplicate-free rows):
+    pyamg would sweep a re-sorted, duplicate-summed copy, which only a Graph on its own does."""
 
     def __init__(self, As, device=None):
-        mats = []
-        for i, A in enumerate(As):
-            A = sp.csr_matrix(A)
-            if A.shape[0] != A.shape[1] or A.shape[0] < 1:
-                raise ValueError(f"matrix {i} of the batch is not square and non-empty: {A.shape}")
+        mats = [sp.csr_matrix(A) for A in As]
+        for i, A in enumerate(mats):
             if not A.has_canonical_format:
                 raise ValueError(f"matrix {i} of the batch has no canonical format (unsorted or "
                                  "duplicate entries); run it through forward() on its own")
-            mats.append(A)
+        self._build(mats, device)
+
+    def _build(self, mats, device):
+        """Every field, from a list of CSR matrices in any stored order."""
+        for i, A in enumerate(mats):
+            if A.shape[0] != A.shape[1] or A.shape[0] < 1:
+                raise ValueError(f"matrix {i} of the batch is not square and non-empty: {A.shape}")
         if not mats:
             raise ValueError("empty batch")
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        dev = torch.device(dev)
+        dev = torch.device(device or torch.device("cuda", torch.cuda.current_device()))
         sizes = np.array([A.shape[0] for A in mats], dtype=np.int64)
         nnzs = np.array([A.nnz for A in mats], dtype=np.int64)
         seg = np.concatenate([[0], np.cumsum(sizes)])
@@ -147,7 +102,7 @@ class GraphBatch:
                               for g, A in enumerate(mats)]).astype(np.int32)
         src = np.repeat(np.arange(n, dtype=np.int32), np.diff(indptr))
         ea = np.concatenate([np.abs(A.data.astype(np.float32)) for A in mats])[:, None]
-        order = np.argsort(tgt, kind="stable")
+        order = np.argsort(tgt, kind="stable")          # each target's edges, ascending source
         tptr = np.zeros(n + 1, dtype=np.int32)
         np.cumsum(np.bincount(tgt, minlength=n), out=tptr[1:])
         self.As = mats
@@ -155,8 +110,6 @@ class GraphBatch:
         self.sizes = sizes
         self.device = dev
         self.seg, self.eseg = SegPtr(seg, dev), SegPtr(eseg, dev)
-        self.node_gid = torch.as_tensor(np.repeat(np.arange(self.nb, dtype=np.int64), sizes),
-                                        device=dev)
         self.crow = torch.as_tensor(indptr, device=dev)
         self.src = torch.as_tensor(src, device=dev)
         self.tgt = torch.as_tensor(tgt, device=dev)
@@ -166,16 +119,26 @@ class GraphBatch:
         self.x = torch.as_tensor(np.repeat((1.0 / sizes).astype(np.float32), sizes)[:, None],
                                  device=dev)
         self.edge_index = torch.stack([self.src.long(), self.tgt.long()])
-        self._gcn = None
-        self._shared = {"plan": None, "kptr": {}}  # shared by the copies with_* make
+        self._shared = {"kptr": {}}  # gcn weights, plan, seed offsets: shared by the copies
+
+    @property
+    def node_gid(self):
+        """Every node's graph id (int64, on the device), made on first use."""
+        if "gid" not in self._shared:
+            gid = np.repeat(np.arange(self.nb, dtype=np.int64), self.sizes)
+            self._shared["gid"] = torch.as_tensor(gid, device=self.device)
+        return self._shared["gid"]
 
     def _copy(self):
-        g = object.__new__(GraphBatch)
+        g = object.__new__(type(self))
         g.__dict__.update(self.__dict__)
         return g
 
     def with_clusters(self, col):
-        """Graph.with_clusters on the stack (col: aggregate column of every node, -1: none)."""
+        """graph_from_matrix(A, Agg) (ns/model/data.py:33-46) from this stack and the device
+        aggregate column of every node (-1: none; agg_op.argmax(axis=1) of an empty row is 0):
+        edge feature 2 = cluster_adj = 0 if both ends are in the same aggregate, else 1. Shares
+        the structure."""
         g = self._copy()
         c = torch.where(col < 0, torch.zeros_like(col), col)
         adj = (c[self.src.long()] != c[self.tgt.long()]).to(torch.float32)
@@ -191,31 +154,84 @@ class GraphBatch:
         g.x = x.reshape(self.n, 1).to(self.device)
         return g
 
-    csr = Graph.csr
+    def csr(self, values):
+        """A DeviceCSR on the stacked pattern with the given per-edge values (fp64 copy)."""
+        from .sparse import DeviceCSR
+        return DeviceCSR.from_torch(self.crow, self.tgt, values.reshape(-1).double().contiguous(),
+                                    (self.n, self.n))
 
     def gcn_weights(self):
-        """Graph.gcn_weights on the stack (per node and per edge: the single graph's bits).
+        """gcn_norm(edge_index, edge_attr[:, 0]) without self loops (TAGConv normalize=True).
         Edge feature 0 never changes, so the copies share the cached weights."""
         if "gcn" not in self._shared:
-            self._shared["gcn"] = Graph.gcn_weights(self)
+            w = self.edge_attr[:, 0].contiguous()
+            dis = torch.empty(self.n, dtype=torch.float32, device=w.device)
+            wn = torch.empty(self.E, dtype=torch.float32, device=w.device)
+            call("mlamg_gnn_gcn_norm", ptr(self.tptr), ptr(self.teid), ptr(self.src),
+                 ptr(self.tgt), ptr(w), int(self.n), int(self.E), ptr(dis), ptr(wn), stream_ptr())
+            self._shared["gcn"] = wn
         return self._shared["gcn"]
+
+    def _seed_ptr(self, key, ks):
+        cache = self._shared["kptr"]
+        if key not in cache:
+            cache[key] = SegPtr(np.concatenate([[0], np.cumsum(ks())]), self.device)
+        return cache[key]
 
     def k_ptr(self, alpha):
         """Offsets of k_g = ceil(alpha n_g) seeds per graph (SegPtr), cached per alpha."""
-        key = float(alpha)
-        cache = self._shared["kptr"]
-        if key not in cache:
-            ks = [int(np.ceil(alpha * int(m))) for m in self.sizes]
-            cache[key] = SegPtr(np.concatenate([[0], np.cumsum(ks)]), self.device)
-        return cache[key]
+        return self._seed_ptr(float(alpha),
+                              lambda: [int(np.ceil(alpha * int(m))) for m in self.sizes])
+
+    def seed_ptr(self, k):
+        """k as seed offsets: a SegPtr as it is; a stack of one graph also takes its seed count."""
+        if isinstance(k, SegPtr):
+            return k
+        if self.nb != 1:
+            raise TypeError("a stack of several graphs takes its seed offsets as a SegPtr")
+        return self._seed_ptr(("k", int(k)), lambda: [int(k)])
 
     def plan(self):
         """The Bellman-Ford level plan of the stacked pattern (graph.BellmanFordSegPlan)."""
-        if self._shared["plan"] is None:
+        if "plan" not in self._shared:
             from .graph import BellmanFordSegPlan
             pattern = self.csr(torch.zeros(self.E, dtype=torch.float32, device=self.device))
             self._shared["plan"] = BellmanFordSegPlan(pattern, self.seg.host)
         return self._shared["plan"]
+
+    def pyamg_sweep(self, C, seeds, kptr, fp64):
+        """pyamg.graph.bellman_ford(C, seeds) per graph, on the cached level plan: (the matrix
+        swept — C itself —, every node's nearest seed as a node id of the stack, -1: none)."""
+        from .graph import bellman_ford_pyamg_seg_device
+        return C, bellman_ford_pyamg_seg_device(self.plan(), C, seeds, kptr.host, fp64=fp64,
+                                                seed_ptr_dev=kptr.dev)[1]
+
+
+class Graph(GraphBatch):
+    """One graph: graph_from_matrix_basic(A) / graph_from_matrix(A, agg) (ns/model/data.py:22-46)
+    on the device, a GraphBatch of A alone. A may have any stored order: the edges keep it."""
+
+    def __init__(self, A, agg=None, device=None):
+        self._build([sp.csr_matrix(A)], device)
+        if agg is not None:
+            col = np.asarray(sp.csr_matrix(agg).argmax(axis=1)).ravel()
+            clustered = self.with_clusters(torch.as_tensor(col, device=self.device))
+            self.edge_attr, self.fe = clustered.edge_attr, clustered.fe
+
+    def pyamg_sweep(self, C, seeds, kptr, fp64):
+        """The same with mlamg_bellman_ford_pyamg, which takes a graph of any size. pyamg's
+        asgraph turns the COO C (agg_interp.py:471) into csr_matrix: columns sorted, duplicate
+        edges summed in C's float32; its sweep visits each row in that order."""
+        from .graph import bellman_ford_pyamg_device
+        from .sparse import DeviceCSR
+        if not self.As[0].has_canonical_format:
+            m, Cs = self.n, C.to_scipy()
+            Cc = sp.coo_matrix((Cs.data.astype(np.float32), (np.repeat(np.arange(m),
+                                np.diff(Cs.indptr)), Cs.indices)), shape=(m, m)).tocsr()
+            Cc.sum_duplicates()
+            C = DeviceCSR.from_scipy(sp.csr_matrix((Cc.data.astype(np.float64), Cc.indices,
+                                                    Cc.indptr), shape=(m, m)), check=False)
+        return C, bellman_ford_pyamg_device(C, seeds, fp64=fp64)[1]
 
 
 # ------------------------------------------------------------------------------------ kernels
@@ -264,7 +280,7 @@ def instance_norm_seg(x, seg, eps=1e-5):
     x = x.contiguous()
     y = torch.empty_like(x)
     call("mlamg_gnn_instance_norm_seg", ptr(x), ptr(seg.dev), seg.host_ptr,
-         int(seg.host.size - 1), int(x.shape[1]), float(eps), ptr(y), stream_ptr())
+         seg.nb, int(x.shape[1]), float(eps), ptr(y), stream_ptr())
     return y
 
 
@@ -276,13 +292,8 @@ def topk_vec_seg(x, seg, kptr):
     vec = torch.empty_like(s)
     idx = torch.empty(max(int(kptr.host[-1]), 1), dtype=torch.int32, device=s.device)
     call("mlamg_gnn_topk_seg", ptr(s), ptr(seg.dev), seg.host_ptr, ptr(kptr.dev), kptr.host_ptr,
-         int(seg.host.size - 1), ptr(vec), ptr(idx), stream_ptr())
+         seg.nb, ptr(vec), ptr(idx), stream_ptr())
     return vec, idx[:int(kptr.host[-1])]
-
-
-def _inorm(g, x):
-    """InstanceNorm over the nodes of every graph in g (a Graph or a GraphBatch)."""
-    return instance_norm_seg(x, g.seg) if isinstance(g, GraphBatch) else instance_norm(x)
 
 
 # ------------------------------------------------------------------------------------ modules
@@ -395,12 +406,12 @@ class MPNN(nn.Module):
     def run(self, g):
         x = g.x
         ea = g.edge_attr
-        x = self.node_conv_in.run(g, _inorm(g, x), ea, act=1, residual=x)
+        x = self.node_conv_in.run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x)
         ea = self.edge_conv_in.run(g, x, ea, act=1, residual=ea)
         for i in range(self.num_internal_conv):
-            x = self.node_convs[i].run(g, _inorm(g, x), ea, act=1, residual=x)
+            x = self.node_convs[i].run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x)
             ea = self.edge_convs[i].run(g, x, ea, act=1, residual=ea)
-        x = self.node_conv_out.run(g, _inorm(g, x), ea, act=1)
+        x = self.node_conv_out.run(g, instance_norm_seg(x, g.seg), ea, act=1)
         ea = self.edge_conv_out.run(g, x, ea, act=1)
         return x, ea
 
@@ -431,7 +442,7 @@ class AggBinarizationLayer(nn.Module):
         if x.dim() == 1:
             x = x.unsqueeze(1)
         for i in range(self.num_conv):
-            x = _inorm(g, x)
+            x = instance_norm_seg(x, g.seg)
             x = self.ncs[i].run(g, x, act=1)        # relu(TAGConv(x))
             for lin in self.fcs[i]:
                 if isinstance(lin, nn.Linear):
@@ -440,10 +451,8 @@ class AggBinarizationLayer(nn.Module):
 
     @torch.no_grad()
     def run(self, g, x, k):
-        """k: the seed count of a Graph, the seed offsets (SegPtr) of a GraphBatch."""
-        if isinstance(g, GraphBatch):
-            return topk_vec_seg(self.run_raw(g, x), g.seg, k)[0]
-        return topk_vec(self.run_raw(g, x), k)[0]
+        """k: the seed offsets per graph (SegPtr); one graph alone also takes its seed count."""
+        return topk_vec_seg(self.run_raw(g, x), g.seg, g.seed_ptr(k))[0]
 
 
 class AggNet(nn.Module):
@@ -495,44 +504,7 @@ class FullAggNet(nn.Module):
         version is unpinned). x: node features replacing the
         reference graph's constant 1/n (graph_from_matrix_basic, ns/model/data.py:22-31) —
         not in the reference's signature; a test hook for well-conditioned inputs."""
-        from .graph import (aggregate_op_device, bellman_ford_device, bellman_ford_pyamg_device,
-                            labels_to_columns)
-        from .sparse import DeviceCSR
-        if aggregation not in ("pyamg", "pyamg64", "parallel"):
-            raise ValueError("aggregation must be 'pyamg', 'pyamg64' or 'parallel', got "
-                             f"{aggregation!r}")
-        A = sp.csr_matrix(A)
-        m = A.shape[0]
-        k = int(np.ceil(alpha * m))
-        g = Graph(A, device=self.device)
-        if x is not None:
-            g.x = torch.as_tensor(x, dtype=torch.float32).reshape(m, 1).to(self.device)
-        node_scores = self.AggNet.run(g, k).reshape(-1)
-        top_k = torch.nonzero(node_scores == 1).reshape(-1)
-        # Bellman-Ford over the CNet edge weights from the seeds (:466-475), on the device
-        _, bf_edges = self.CNet.run(g)
-        C = g.csr(bf_edges)
-        seeds = top_k.to(torch.int32)
-        if aggregation != "parallel" and not A.has_canonical_format:
-            # pyamg's asgraph turns the COO C (:471) into csr_matrix: columns sorted, duplicate
-            # edges summed in C's float32; its sweep visits each row in that order
-            Cs = C.to_scipy()
-            Cc = sp.coo_matrix((Cs.data.astype(np.float32), (np.repeat(np.arange(m),
-                                np.diff(Cs.indptr)), Cs.indices)), shape=(m, m)).tocsr()
-            Cc.sum_duplicates()
-            C = DeviceCSR.from_scipy(sp.csr_matrix((Cc.data.astype(np.float64), Cc.indices,
-                                                    Cc.indptr), shape=(m, m)), check=False)
-        if aggregation != "parallel":
-            _, lab, _ = bellman_ford_pyamg_device(C, seeds, fp64=aggregation == "pyamg64")
-            if bool((lab < 0).any()):
-                raise KeyError(-1)
-        else:
-            _, lab, _ = bellman_ford_device(C.T, seeds)
-        col = labels_to_columns(lab, seeds)
-        Agg = aggregate_op_device(col, k)
-        # P_hat from PNet on graph_from_matrix(A, Agg), P = P_hat Agg (:476-484)
-        _, p_edges = self.PNet.run(g.with_clusters(col))
-        P = g.csr(p_edges) @ Agg
+        st = self.forward_stack(Graph(A, device=self.device), alpha, aggregation, x, strict=True)
 
         def to_t(M, dtype=torch.float32):
             crow, cj, v = M.to_torch()
@@ -541,43 +513,47 @@ class FullAggNet(nn.Module):
             return torch.sparse_coo_tensor(torch.stack([rows, cj.long()]), v.to(dtype),
                                            M.shape).coalesce()
 
-        return to_t(Agg), to_t(P), to_t(C), top_k, node_scores
+        return (to_t(st["Agg"]), to_t(st["P"]), to_t(st["C"]), st["top_k"], st["node_scores"])
 
     @torch.no_grad()
-    def forward_stack(self, batch, alpha, aggregation="pyamg", x=None):
-        """forward() on every graph of a GraphBatch at once, results still stacked: a dict with
-        Agg, P, C (DeviceCSR on stack rows; Agg and P on stacked aggregate columns), top_k (seed
-        node ids in the stack, ascending), node_scores, kptr (SegPtr: seed / column offsets per
-        graph) and failed (numpy bool per graph: some node reached by no seed; "parallel" never
-        fails). The steps are forward()'s, each one call on the stack; InstanceNorm, top-k and
-        pyamg's sweep run their segmented kernels, so every graph's part carries the bits of
-        its own forward(). Launches and host synchronisations do not depend on the batch size."""
-        from .graph import (aggregate_op_device, bellman_ford_device,
-                            bellman_ford_pyamg_seg_device, labels_to_columns)
+    def forward_stack(self, batch, alpha, aggregation="pyamg", x=None, strict=False):
+        """The forward pass (:442-486) on every graph of `batch`, a GraphBatch or a Graph (a
+        batch of one; nothing else is accepted), at once, results still stacked: a dict with
+        Agg, P, C (DeviceCSR on stack rows; Agg and P on stacked aggregate columns; C as pyamg
+        swept it), top_k (seed node ids in the
+        stack, ascending), node_scores, kptr (SegPtr: seed / column offsets per graph) and failed
+        (numpy bool per graph: some node reached by no seed; "parallel" never fails; strict:
+        KeyError(-1) instead, before PNet runs). Every step is one call on the stack, so
+        launches and host synchronisations do not depend on the batch size, and every graph's
+        part carries the bits it has when the graph runs alone."""
+        from .graph import aggregate_op_device, bellman_ford_device, labels_to_columns
         if aggregation not in ("pyamg", "pyamg64", "parallel"):
             raise ValueError("aggregation must be 'pyamg', 'pyamg64' or 'parallel', got "
                              f"{aggregation!r}")
-        if not isinstance(batch, GraphBatch):
-            raise TypeError("forward_batch takes a GraphBatch")
         g = batch if x is None else batch.with_x(x)
         kptr = batch.k_ptr(alpha)
         node_scores = self.AggNet.run(g, kptr).reshape(-1)
         top_k = torch.nonzero(node_scores == 1).reshape(-1)  # k_g per graph, graph after graph
+        # Bellman-Ford over the CNet edge weights from the seeds (:466-475), on the device
         _, bf_edges = self.CNet.run(g)
         C = g.csr(bf_edges)
         seeds = top_k.to(torch.int32)
         failed = np.zeros(batch.nb, dtype=bool)
         if aggregation != "parallel":
-            _, lab, _ = bellman_ford_pyamg_seg_device(batch.plan(), C, seeds, kptr.host,
-                                                      fp64=aggregation == "pyamg64",
-                                                      seed_ptr_dev=kptr.dev)
-            lost = torch.zeros(batch.nb, dtype=torch.int32, device=lab.device)
-            lost.index_add_(0, batch.node_gid, (lab < 0).to(torch.int32))
-            failed = lost.cpu().numpy() > 0
+            C, lab = batch.pyamg_sweep(C, seeds, kptr, aggregation == "pyamg64")
+            if batch.nb == 1:  # one reduction instead of the count per graph
+                failed = np.array([bool((lab < 0).any())])
+            else:
+                lost = torch.zeros(batch.nb, dtype=torch.int32, device=lab.device)
+                lost.index_add_(0, batch.node_gid, (lab < 0).to(torch.int32))
+                failed = lost.cpu().numpy() > 0
+            if strict and failed.any():
+                raise KeyError(-1)
         else:
             _, lab, _ = bellman_ford_device(C.T, seeds)
         col = labels_to_columns(lab, seeds)
         Agg = aggregate_op_device(col, int(kptr.host[-1]))
+        # P_hat from PNet on graph_from_matrix(A, Agg), P = P_hat Agg (:476-484)
         _, p_edges = self.PNet.run(g.with_clusters(col))
         P = g.csr(p_edges) @ Agg
         return dict(Agg=Agg, P=P, C=C, top_k=top_k, node_scores=node_scores, kptr=kptr,

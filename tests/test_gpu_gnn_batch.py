@@ -1,6 +1,7 @@
 """GPU: batched FullAggNet inference. The three segmented kernels (mlamg_gnn_instance_norm_seg,
 mlamg_gnn_topk_seg, mlamg_bellman_ford_pyamg_seg) against the single-graph entry points on every
-segment alone (bitwise) and against the float64 / oracle references; their refusals; then
+segment alone (bitwise) and against the float64 / oracle references; the single entry points as
+the segmented ones on one segment (mlamg_gnn_topk on its cached scratch); their refusals; then
 FullAggNet.forward_batch against forward() graph by graph, bitwise in every tensor, and
 mlamg.fitness against the loop forward() -> amg_2_v().
 
@@ -127,6 +128,72 @@ def test_topk_seg(torch_cuda, shift):
         assert np.array_equal(mine_v.cpu().numpy().view(np.uint32), rvec.view(np.uint32)), (g, k)
         assert np.array_equal(mine_i.cpu().numpy() - a, ridx), (g, k)
         assert int((mine_v == 1).sum()) == k and int((mine_v == 0).sum()) == n - k
+
+
+# ------------------------------------------------------------- one segment is the single call
+@pytest.mark.parametrize("n", SIZES)
+def test_one_segment_is_the_single_call(torch_cuda, n):
+    """The single entry points run the segmented kernels with null offsets: offsets [0, n] given
+    explicitly are the same call, bit for bit."""
+    torch = torch_cuda
+    from mlamg import gnn
+    g = SIZES.index(n)
+    seg = _seg(torch, [n])
+    for F in (1, 8, 64):
+        X = torch.as_tensor(_norm_input(F)[0][g]).cuda()
+        stacked, single = gnn.instance_norm_seg(X, seg), gnn.instance_norm(X)
+        assert torch.equal(stacked.view(torch.int32), single.view(torch.int32)), (n, F)
+    s = torch.as_tensor(_topk_scores()[g]).cuda()
+    for k in _k_choices(n):
+        vec, idx = gnn.topk_vec_seg(s, seg, _seg(torch, [k]))
+        svec, sidx = gnn.topk_vec(s, k)
+        assert torch.equal(vec.view(torch.int32), svec.view(torch.int32)), (n, k)
+        assert idx.dtype == sidx.dtype and torch.equal(idx, sidx), (n, k)
+
+
+def test_topk_single_on_cached_scratch(torch_cuda):
+    """mlamg_gnn_topk keeps its sort storage in a cached block: a larger earlier call leaves
+    nothing behind in a smaller later one, and the same input gives the same bits again. The
+    entry synchronises: the results are read on another (non-blocking) stream straight after it
+    returns, with no synchronisation in between."""
+    torch = torch_cuda
+    from mlamg._lib import call, ptr
+    from oracle import gnn_kernels_ref as kref
+    scores = dict(zip(SIZES, _topk_scores()))
+    work, side = torch.cuda.Stream(), torch.cuda.Stream()
+
+    def run(s_np, k, with_idx=True):
+        s = torch.as_tensor(s_np).cuda()
+        vec = torch.full((s.numel(),), float("nan"), dtype=torch.float32, device="cuda")
+        idx = torch.full((max(k, 1),), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()  # the inputs are in place before `work` reads them
+        call("mlamg_gnn_topk", ptr(s), int(s.numel()), int(k), ptr(vec),
+             ptr(idx) if with_idx else None, ctypes.c_void_p(work.cuda_stream))
+        with torch.cuda.stream(side):
+            v, i = vec.cpu().numpy(), idx.cpu().numpy()[:k]
+        rvec, ridx = kref.topk(s_np, k)
+        assert np.array_equal(v.view(np.uint32), rvec.view(np.uint32)), (s_np.size, k)
+        if with_idx:
+            assert np.array_equal(i, ridx), (s_np.size, k)
+        else:
+            assert np.all(idx.cpu().numpy() == -1)  # NULL idx: nothing is written for it
+        return v
+
+    first = run(scores[1000], 100)
+    run(np.array([-0.0, 0.0], dtype=np.float32), 1)
+    run(scores[257], 257)
+    last = run(scores[1000], 100, with_idx=False)
+    assert np.array_equal(first.view(np.uint32), last.view(np.uint32))
+
+
+def test_topk_single_refusals(torch_cuda):
+    torch = torch_cuda
+    s = torch.arange(5, dtype=torch.float32, device="cuda")
+    vec = torch.full((5,), float("nan"), dtype=torch.float32, device="cuda")
+    idx = torch.full((6,), -1, dtype=torch.int32, device="cuda")
+    _einval(torch, "mlamg_gnn_topk", s, 5, 6, vec, idx)  # k > n
+    _einval(torch, "mlamg_gnn_topk", s, 2 ** 31 - 1, 0, vec, idx)  # past the int32 node ids
+    assert bool(vec.isnan().all()) and idx.cpu().tolist() == [-1] * 6
 
 
 # ---------------------------------------------------------------------- segmented Bellman-Ford
