@@ -32,6 +32,7 @@
 // descriptor and the LDS sizes that planner and kernels share). Every floating-point operation
 // runs in the kernels here.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -54,24 +55,6 @@ constexpr int kBWaves = kBT / 64;
 template <class T>
 __device__ __forceinline__ T* at(char* base, int64_t off) {
   return reinterpret_cast<T*>(base + off);
-}
-
-__device__ __forceinline__ double bw_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// fixed-order workgroup sum (wave butterflies, then the 16 wave totals left to right)
-__device__ double block_sum(double v, double* red) {
-  v = bw_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < kBWaves; ++w) t += red[w];
-  __syncthreads();
-  return t;
 }
 
 // wave argmax of (v, idx), ties to the smaller idx; lane 0 of each wave posts it
@@ -218,7 +201,7 @@ __device__ __forceinline__ void rows_dot(const double* __restrict__ M, int nc,
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-      const double t = bw_sum(sum[r]);
+      const double t = wave_sum(sum[r]);
       const int j = j0 + r * kBWaves;
       if (lane == 0 && j < nc) out[j] = t;
     }
@@ -1141,7 +1124,7 @@ __global__ __launch_bounds__(256) void k_amg2v_coarse(const BDesc* __restrict__ 
 #pragma unroll
     for (int u = 0; u < 4; ++u) s = fma(m[u], x[u], s);
   }
-  s = bw_sum(s);
+  s = wave_sum(s);
   if (lane == 0) out[row] = s;
 }
 
@@ -1586,7 +1569,8 @@ __global__ __launch_bounds__(kBT) void k_amg2v_cycles(const BDesc* __restrict__ 
       #pragma unroll 1
       for (int i = tid; i < n; i += kBT) part += xs[i] * xs[i];
     }
-    const double nrm = sqrt(block_sum(part, redv));
+    const double nrm = sqrt(block_sum_all<kBT>(part, redv));
+    __syncthreads();  // redv is posted again by the next norm
     if (tid == 0) err[itn] = nrm;
     return D.tol >= 0.0 && nrm <= D.tol;
   };

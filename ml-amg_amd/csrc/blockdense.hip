@@ -21,6 +21,7 @@
 // pivot column and the pivot indices are 130 of the CU's 160 KiB) and in its own slice of the
 // handle's inverse buffer otherwise.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <memory>
 
@@ -251,10 +252,7 @@ __global__ __launch_bounds__(256) void k_bd_gemv_mv(const double* __restrict__ i
       }
     }
 #pragma unroll
-    for (int c = 0; c < kBdCT; ++c) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_xor(s[c], off, 64);
-    }
+    for (int c = 0; c < kBdCT; ++c) s[c] = wave_sum(s[c]);
     if (lane == 0) {
 #pragma unroll
       for (int c = 0; c < kBdCT; ++c)

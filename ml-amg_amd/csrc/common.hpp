@@ -249,26 +249,6 @@ struct mlamg_dense {
 };
 
 namespace mlamg {
-// s = p[start] + p[start+step] + ... in that order (bitwise a plain strided loop), with the loads
-// issued 8 at a time: a one-workgroup reduction over tens of thousands of partials is otherwise
-// a chain of dependent memory round trips.
-__device__ __forceinline__ double strided_sum(const double* __restrict__ p, int n, int start,
-                                              int step) {
-  double s = 0.0;
-  int i = start;
-  for (; i + 7 * step < n; i += 8 * step) {
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = p[i + u * step];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += v[u];
-  }
-  for (; i < n; i += step) s += p[i];
-  return s;
-}
-}  // namespace mlamg
-
-namespace mlamg {
 // Upper bound on the per-block partial sums a NORM launch of A can write, whatever format is
 // active (CSR-stream: n_blocks; SELL-64: n/256; CSR-vector: n*VW/256 <= n/4), plus one slot.
 // Wide CSR-vector widths (128..512 lanes per row, one workgroup of 512 lanes) write one partial

@@ -14,6 +14,7 @@
 // elimination with partial pivoting (one pivot launch + one elimination launch per column),
 // which also reports an exactly singular operator like spla.factorized fails.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -131,8 +132,7 @@ __global__ __launch_bounds__(256) void k_gemv(const double* __restrict__ M, int6
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += m[u] * v[u];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if (lane == 0) x[row] = s;
 }
 
@@ -162,8 +162,7 @@ __global__ __launch_bounds__(256) void k_gemv_tri(const double* __restrict__ M, 
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += m[u] * v[u];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if (lane == 0) x[row] = s;
 }
 

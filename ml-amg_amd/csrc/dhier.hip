@@ -25,23 +25,15 @@
 // otherwise the replicated tail alone replays its own.
 #include "comm.hpp"
 #include "cycle.hpp"
+#include "reduce.hpp"
 
 namespace mlamg {
 
 // sum the residual partials of this rank into partial[n] (fixed order)
 __global__ __launch_bounds__(1024) void k_local_sum(double* __restrict__ partial, int n) {
   __shared__ double red[16];
-  double s = 0.0;
-  s = strided_sum(partial, n, threadIdx.x, 1024);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    partial[n] = t;
-  }
+  const double t = partials_total<1024>(partial, n, red);
+  if (threadIdx.x == 0) partial[n] = t;
 }
 
 __global__ void k_norm_finish(const double* __restrict__ sum, double* hist, int32_t* counter,

@@ -12,39 +12,17 @@
 // to bisect the tridiagonal T_j for its largest eigenvalue. Reductions use a fixed order, so
 // the result is deterministic.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 
 namespace mlamg {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ double block_sum256(double v, double* red) {
-  v = wsum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = ((red[0] + red[1]) + red[2]) + red[3];
-  __syncthreads();
-  return t;
-}
-
 __global__ __launch_bounds__(1024) void k_reduce_to(const double* __restrict__ partial, int n,
                                                     double* __restrict__ out, int take_sqrt) {
   __shared__ double red[16];
-  double s = 0.0;
-  s = strided_sum(partial, n, threadIdx.x, 1024);
-  s = wsum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    *out = take_sqrt ? sqrt(t) : t;
-  }
+  const double t = partials_total<1024>(partial, n, red);
+  if (threadIdx.x == 0) *out = take_sqrt ? sqrt(t) : t;
 }
 
 // partial[b] = sum over the block's entries of z_i q_i
@@ -55,7 +33,8 @@ __global__ __launch_bounds__(256) void k_lz_dot(const double* __restrict__ z,
   double acc = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     acc += z[i] * q[i];
-  const double t = block_sum256(acc, red);
+  const double t = block_sum_all<256>(acc, red);
+  __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -77,7 +56,8 @@ __global__ __launch_bounds__(256) void k_lz_update(const double* __restrict__ z,
     w[i] = wi;
     acc += d[i] * (wi * wi);
   }
-  const double t = block_sum256(acc, red);
+  const double t = block_sum_all<256>(acc, red);
+  __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -118,7 +98,8 @@ __global__ __launch_bounds__(256) void k_lz_init(const int32_t* __restrict__ ind
     q[i] = x;
     acc += di * (x * x);
   }
-  const double t = block_sum256(acc, red);
+  const double t = block_sum_all<256>(acc, red);
+  __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 

@@ -18,6 +18,7 @@
 // operations as scipy's numpy code), so an inner iteration costs one status read; the
 // triangular solve and the restart logic stay on the host, once per restart cycle.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 
@@ -26,10 +27,12 @@ namespace mlamg {
 constexpr int kGmThreads = 256;
 constexpr int kGmMaxBlocks = 1024;
 
-__device__ __forceinline__ double gm_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
+// sum of np partials by a whole workgroup of kGmThreads, every thread gets it; behind a barrier,
+// because red may still be read from the sum before
+__device__ __forceinline__ double gm_total(const double* __restrict__ partial, int np,
+                                           double* red) {
+  __syncthreads();
+  return partials_total_all<kGmThreads>(partial, np, red);
 }
 
 // out[0] = a . b, fixed order: per-workgroup partials, summed in order by the last-arriving
@@ -45,11 +48,9 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_dot(const double* __restrict_
   for (int64_t i = blockIdx.x * (int64_t)kGmThreads + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kGmThreads)
     s += a[i] * b[i];
-  s = gm_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  s = block_sum<kGmThreads>(s, red);
   if (threadIdx.x == 0) {
-    partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    partial[blockIdx.x] = s;
     __threadfence();
     const int prev = __hip_atomic_fetch_add(ctr, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
     last = prev == (int)gridDim.x - 1;
@@ -58,12 +59,8 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_dot(const double* __restrict_
   __syncthreads();
   if (!last) return;
   __threadfence();
-  double t = strided_sum(partial, gridDim.x, threadIdx.x, kGmThreads);
-  t = gm_wave_sum(t);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = ((red[0] + red[1]) + red[2]) + red[3];
+  const double t = gm_total(partial, gridDim.x, red);
+  if (threadIdx.x == 0) *out = t;
 }
 
 // The inner loop's dots without the arrival counter: k_gm_part writes k_gm_dot's per-workgroup
@@ -80,20 +77,8 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_part(const double* __restrict
   for (int64_t i = blockIdx.x * (int64_t)kGmThreads + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kGmThreads)
     s += a[i] * b[i];
-  s = gm_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// sum of np partials by a whole workgroup of kGmThreads, k_gm_dot's order; every thread gets it
-__device__ double gm_total(const double* __restrict__ partial, int np, double* red) {
-  double t = strided_sum(partial, np, threadIdx.x, kGmThreads);
-  t = gm_wave_sum(t);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+  s = block_sum<kGmThreads>(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // w -= c v with c = the dot k_gm_part left in partial (every workgroup sums it; workgroup 0
@@ -156,11 +141,6 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_update(double* __restrict__ x
     for (int k = 0; k < m; ++k) t += y[k] * V[k * ld + i];
     x[i] = x[i] + t;
   }
-}
-
-static int gm_grid(int64_t n) {
-  return (int)std::min<int64_t>(kGmMaxBlocks, std::max<int64_t>(1, (n + kGmThreads - 1) /
-                                                                       kGmThreads));
 }
 
 // LAPACK dlartg (3.10+, the safe-scaling version scipy's get_lapack_funcs('lartg') binds):
@@ -303,7 +283,7 @@ int gmres_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, double* x, do
   MLAMG_HIP(hipMemsetAsync(W.ctr, 0, 64, s));
   MLAMG_TRY(hier_prepare_ext(M));  // allocates the hierarchy's flags and work buffers
   MLAMG_HIP(hipMemsetAsync(hier_done_flag(M), 0, sizeof(int32_t), s));
-  const int nb = gm_grid(n);
+  const int nb = reduce_grid(n, kGmThreads, kGmMaxBlocks);
   const int norm_slot = restart + 1;
 
   auto dot = [&](const double* a, const double* c, int slot) -> int {
@@ -550,11 +530,11 @@ int gmres_householder_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, d
   MLAMG_HIP(hipMemsetAsync(ctr, 0, 64, s));
   MLAMG_TRY(hier_prepare_ext(M));
   MLAMG_HIP(hipMemsetAsync(hier_done_flag(M), 0, sizeof(int32_t), s));
-  const int nb = gm_grid(n);
+  const int nb = reduce_grid(n, kGmThreads, kGmMaxBlocks);
   auto Wk = [&](int k) { return Wv + (int64_t)k * ld; };
   auto dotv = [&](const double* a, const double* c, int64_t len, double* out) -> int {
-    hipLaunchKernelGGL(k_gm_dot, dim3(gm_grid(len)), dim3(kGmThreads), 0, s, a, c, len, partial,
-                       ctr, scal, nullptr);
+    hipLaunchKernelGGL(k_gm_dot, dim3(reduce_grid(len, kGmThreads, kGmMaxBlocks)),
+                       dim3(kGmThreads), 0, s, a, c, len, partial, ctr, scal, nullptr);
     MLAMG_HIP(hipGetLastError());
     MLAMG_HIP(hipMemcpyAsync(out, scal, sizeof(double), hipMemcpyDeviceToHost, s));
     MLAMG_HIP(hipStreamSynchronize(s));

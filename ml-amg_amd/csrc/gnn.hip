@@ -9,6 +9,7 @@
 // transpose lists a target's incoming edges with ascending source), so every aggregation is
 // deterministic. Dense layers use torch's Linear layout (weight [out, in], y = x W^T + b).
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -16,17 +17,6 @@ namespace mlamg {
 namespace {
 
 constexpr int kT = 256;
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ float wsumf(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Every kernel walks its items with this loop: block b takes items [b * per, (b + 1) * per),
 // this thread item `sub` of them, then the block strides on by the whole grid. blocks() below
@@ -117,23 +107,14 @@ __global__ void k_inorm_seg(const float* __restrict__ Xs, const int64_t* __restr
     float* Y = Ys + a * F;
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kT) s += X[i * F + f];
-    s = wsum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = s;
-    __syncthreads();
-    double tot = 0.0;
-    for (int w = 0; w < kT / 64; ++w) tot += red[w];
-    const double mean = tot / (double)n;
+    const double mean = block_sum_all<kT>(s, red) / (double)n;
     __syncthreads();
     double v = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += kT) {
       const double d = X[i * F + f] - mean;
       v += d * d;
     }
-    v = wsum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = v;
-    __syncthreads();
-    double vt = 0.0;
-    for (int w = 0; w < kT / 64; ++w) vt += red[w];
+    const double vt = block_sum_all<kT>(v, red);
     const float inv = (float)(1.0 / sqrt(vt / (double)n + (double)eps));
     const float mf = (float)mean;
     for (int64_t i = threadIdx.x; i < n; i += kT) Y[i * F + f] = (X[i * F + f] - mf) * inv;
@@ -247,12 +228,12 @@ __global__ void k_edge_mlp(const int32_t* __restrict__ src, const int32_t* __res
       for (int k = 0; k < fe; ++k) h = fmaf(a[k], w1t[(2 * F + k) * H + lane], h);
       h = fmaxf(h + b1[lane], 0.0f);
     }
-    const float mean = wsumf(lane < H ? h : 0.0f) / (float)H;
+    const float mean = wave_sum(lane < H ? h : 0.0f) / (float)H;
     const float d = lane < H ? h - mean : 0.0f;
-    const float var = wsumf(d * d) / (float)H;
+    const float var = wave_sum(d * d) / (float)H;
     const float hn = lane < H ? (d / sqrtf(var + 1e-5f)) * g[lane] + beta[lane] : 0.0f;
     for (int c = 0; c < C; ++c) {
-      float y = wsumf(lane < H ? hn * W2[c * H + lane] : 0.0f) + b2[c];
+      float y = wave_sum(lane < H ? hn * W2[c * H + lane] : 0.0f) + b2[c];
       if (act == 1) y = fmaxf(y, 0.0f);
       if (R) y = y + R[e * rc + (rc == 1 ? 0 : c)];
       if (lane == 0) out[e * C + c] = y;

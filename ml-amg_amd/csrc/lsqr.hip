@@ -15,6 +15,7 @@
 //   ddnorm, tests, istop
 // The host checks the flag every kLsqrChunk iterations.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 #include <limits>
@@ -23,7 +24,6 @@ namespace mlamg {
 
 namespace {
 constexpr int kLsqrChunk = 8;
-constexpr int kLsqrBlocks = 512;  // fixed grid of the vector kernels: fixed reduction order
 
 struct LsqrState {
   double alfa, beta, anorm, ddnorm, xnorm, xxnorm, z, cs2, sn2, rhobar, phibar, bnorm, res2;
@@ -31,23 +31,6 @@ struct LsqrState {
   double atol, btol, ctol;
   int32_t done, istop, itn, iter_lim;
 };
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < 4; ++i) t += red[i];
-  return t;
-}
-
-// single-workgroup fixed-order sum of the kLsqrBlocks partials (thread 0 gets it)
-__device__ __forceinline__ double partial_total(const double* __restrict__ p, double* red) {
-  double s = strided_sum(p, kLsqrBlocks, threadIdx.x, 256);
-  return block_sum(s, red);
-}
 
 // u = t - alfa*u; partial sums of u^2
 __global__ __launch_bounds__(256) void k_ls_u(const double* __restrict__ t, double* __restrict__ u,
@@ -61,7 +44,7 @@ __global__ __launch_bounds__(256) void k_ls_u(const double* __restrict__ t, doub
     u[i] = ui;
     sq += ui * ui;
   }
-  const double b = block_sum(sq, red);
+  const double b = block_sum<256>(sq, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = b;
 }
 
@@ -69,7 +52,7 @@ __global__ __launch_bounds__(256) void k_ls_u(const double* __restrict__ t, doub
 __global__ __launch_bounds__(256) void k_ls_beta(const double* __restrict__ partial, LsqrState* st) {
   __shared__ double red[4];
   if (st->done) return;
-  const double s = partial_total(partial, red);
+  const double s = partials_total<256>(partial, kSumGrid, red);
   if (threadIdx.x == 0) {
     const double beta = sqrt(s);
     st->beta = beta;
@@ -102,7 +85,7 @@ __global__ __launch_bounds__(256) void k_ls_v(const double* __restrict__ t, doub
     v[i] = vi;
     sq += vi * vi;
   }
-  const double s = block_sum(sq, red);
+  const double s = block_sum<256>(sq, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(256) void k_ls_step(const double* __restrict__ part
   __shared__ double red[4];
   if (st->done) return;
   const bool bpos = st->beta > 0.0;
-  const double s = bpos ? partial_total(partial, red) : 0.0;
+  const double s = bpos ? partials_total<256>(partial, kSumGrid, red) : 0.0;
   if (threadIdx.x != 0) return;
   st->itn += 1;
   double alfa = st->alfa;
@@ -195,7 +178,7 @@ __global__ __launch_bounds__(256) void k_ls_update(double* __restrict__ v, doubl
     x[i] = x[i] + t1 * wi;
     w[i] = vi + t2 * wi;
   }
-  const double s = block_sum(sq, red);
+  const double s = block_sum<256>(sq, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -203,7 +186,7 @@ __global__ __launch_bounds__(256) void k_ls_update(double* __restrict__ v, doubl
 __global__ __launch_bounds__(256) void k_ls_test(const double* __restrict__ partial, LsqrState* st) {
   __shared__ double red[4];
   if (st->done) return;
-  const double s = partial_total(partial, red);
+  const double s = partials_total<256>(partial, kSumGrid, red);
   if (threadIdx.x != 0) return;
   const double eps = std::numeric_limits<double>::epsilon();
   const double dkn = sqrt(s);
@@ -227,20 +210,20 @@ __global__ __launch_bounds__(256) void k_ls_test(const double* __restrict__ part
   if (istop != 0) st->done = 1;
 }
 
-// sum of squares of a vector into partial[0..kLsqrBlocks)
+// sum of squares of a vector into partial[0..kSumGrid)
 __global__ __launch_bounds__(256) void k_ls_sq(const double* __restrict__ a, int64_t n,
                                                double* partial) {
   __shared__ double red[4];
   double sq = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     sq += a[i] * a[i];
-  const double s = block_sum(sq, red);
+  const double s = block_sum<256>(sq, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void k_ls_total(const double* __restrict__ partial, double* out) {
   __shared__ double red[4];
-  const double s = partial_total(partial, red);
+  const double s = partials_total<256>(partial, kSumGrid, red);
   if (threadIdx.x == 0) *out = s;
 }
 
@@ -251,7 +234,7 @@ __global__ __launch_bounds__(256) void k_ls_sum(const double* __restrict__ a, in
   double acc = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     acc += a[i];
-  const double s = block_sum(acc, red);
+  const double s = block_sum<256>(acc, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -281,7 +264,7 @@ int mlamg_lsqr(const mlamg_csr* A, const mlamg_csr* AT, const double* b, double*
   hipStream_t s = S(stream);
   const int64_t m = A->n_rows, n = A->n_cols;
   if (iter_lim <= 0) iter_lim = (int)std::min<int64_t>(2 * n, (int64_t)1 << 30);
-  const int nb = kLsqrBlocks;
+  const int nb = kSumGrid;
   const unsigned gm = (unsigned)nb;
   double *u = nullptr, *v = nullptr, *w = nullptr, *t = nullptr, *partial = nullptr;
   LsqrState* st = nullptr;
@@ -390,12 +373,12 @@ int mlamg_remove_mean(double* x, int64_t n, void* stream) {
   MLAMG_REQUIRE(n >= 0 && (n == 0 || x), "NULL argument");
   if (n == 0) return MLAMG_OK;
   hipStream_t s = S(stream);
-  double* partial = static_cast<double*>(scratch(sizeof(double) * (kLsqrBlocks + 1), 1));
+  double* partial = static_cast<double*>(scratch(sizeof(double) * (kSumGrid + 1), 1));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
-  hipLaunchKernelGGL(k_ls_sum, dim3(kLsqrBlocks), dim3(256), 0, s, x, n, partial);
-  hipLaunchKernelGGL(k_ls_total, dim3(1), dim3(256), 0, s, partial, partial + kLsqrBlocks);
-  hipLaunchKernelGGL(k_ls_sub_mean, dim3(kLsqrBlocks), dim3(256), 0, s, x, n,
-                     partial + kLsqrBlocks);
+  hipLaunchKernelGGL(k_ls_sum, dim3(kSumGrid), dim3(256), 0, s, x, n, partial);
+  hipLaunchKernelGGL(k_ls_total, dim3(1), dim3(256), 0, s, partial, partial + kSumGrid);
+  hipLaunchKernelGGL(k_ls_sub_mean, dim3(kSumGrid), dim3(256), 0, s, x, n,
+                     partial + kSumGrid);
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;
 }

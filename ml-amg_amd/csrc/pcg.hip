@@ -18,6 +18,7 @@
 // fixed grid, summed in order by the kernel that consumes the scalar), so a solve is
 // deterministic.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <cmath>
 
@@ -58,18 +59,12 @@ namespace mlamg {
 constexpr int kPcgThreads = 256;
 constexpr int kPcgMaxBlocks = 1024;
 
-__device__ __forceinline__ double pcg_wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
+// the workgroup's sum -> partial[blockIdx.x]; an LDS array of its own, so a kernel may post here
+// while slower waves still read last_total's
 __device__ __forceinline__ void block_partial(double s, double* partial) {
   __shared__ double red[kPcgThreads / 64];
-  s = pcg_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  s = block_sum<kPcgThreads>(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // Each reduction kernel finishes its own scalar step: every workgroup writes its partial, and the
@@ -96,11 +91,7 @@ __device__ __forceinline__ bool arrive_last(int32_t* ctr) {
 // fixed-order sum of nb partials by one kPcgThreads workgroup (all threads get the total)
 __device__ __forceinline__ double last_total(const double* __restrict__ partial, int nb) {
   __shared__ double red[kPcgThreads / 64];
-  double s = strided_sum(partial, nb, threadIdx.x, kPcgThreads);
-  s = pcg_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
+  return partials_total_all<kPcgThreads>(partial, nb, red);
 }
 
 // x = 0, r = b, ||b||^2; done := outer done (a finished outer iteration skips the solve); a zero
@@ -259,11 +250,6 @@ __global__ void k_pcg_end(double* scal, int32_t* done, int32_t* flags, const int
   *done = 1;
 }
 
-static int pcg_grid(int64_t n) {
-  return (int)std::min<int64_t>(kPcgMaxBlocks, std::max<int64_t>(1, (n + kPcgThreads - 1) /
-                                                                        kPcgThreads));
-}
-
 static int pcg_iteration(mlamg_pcg* C, double* x, int32_t* done, int it, hipStream_t s) {
   const int nb = C->nb;
   const int64_t n = C->n;
@@ -358,17 +344,15 @@ __global__ __launch_bounds__(256) void k_sym_check(const int32_t* __restrict__ i
 // ---------------------------------------------------------------- block (n x k) solve
 // The iteration above on every column of a row-major n x k block at once. Column j keeps the bits
 // of the single solve on column j: the reduction kernels walk the rows exactly as the single
-// kernels do (nb = pcg_grid(n) workgroups of 256 on blockIdx.x, thread t of block b takes the rows
-// b*256 + t + m*nb*256, the wave butterfly, ((red0+red1)+red2)+red3) with one accumulator per
-// column of a tile of kPcgCT columns (blockIdx.y; spmm.hip's k_colsum_partial), partials at
+// kernels do (the same nb workgroups of 256 on blockIdx.x, thread t of block b takes the rows
+// b*256 + t + m*nb*256, reduce.hpp's order from there) with one accumulator per column of a
+// tile of kColTile columns (blockIdx.y; tile_sum, as spmm.hip's k_colsum_partial), partials at
 // [col * nb + b]; the consumer sums a column's partials in last_total's order (col_total: one
 // wave plays the four waves of last_total's workgroup). No arrival counter, as above. Every
 // column has its scalars (scal's layout at sc + 8 col), a done flag and an iteration counter; a
 // done column is frozen (nothing of it is read or written any more). The thread that marks the
 // last column done raises the all-done flag st[0], which the host polls and every launch of the
 // preconditioner's block cycle tests.
-constexpr int kPcgCT = 8;  // columns per thread in the block kernels (spmm.hip kMvCT)
-
 __device__ __forceinline__ int32_t* col_done(int32_t* st, int c) { return st + 8 + 2 * c; }
 __device__ __forceinline__ int32_t* col_iters(int32_t* st, int c) { return st + 9 + 2 * c; }
 
@@ -398,8 +382,8 @@ __device__ __forceinline__ double col_total(const double* __restrict__ partial, 
   double w[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u)
-    w[u] = pcg_wave_sum(strided_sum(partial, nb, lane + 64 * u, kPcgThreads));
-  return ((w[0] + w[1]) + w[2]) + w[3];
+    w[u] = wave_sum(strided_sum(partial, nb, lane + 64 * u, kPcgThreads));
+  return waves_total<kPcgThreads>(w);
 }
 
 // bit c set: column c0 + c of the tile exists and is not done
@@ -421,20 +405,12 @@ __device__ __forceinline__ unsigned tile_live(const int32_t* st, int c0, int nc)
 }
 
 // the tile's per-column block sums -> partial[(c0 + c) * gridDim.x + blockIdx.x] (live columns)
-__device__ __forceinline__ void tile_partials(double (&acc)[kPcgCT], unsigned live, int c0,
+__device__ __forceinline__ void tile_partials(double (&acc)[kColTile], unsigned live, int c0,
                                               double* __restrict__ partial) {
-  __shared__ double red[kPcgThreads / 64][kPcgCT];
-#pragma unroll
-  for (int c = 0; c < kPcgCT; ++c) {
-    const double w = pcg_wave_sum(acc[c]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
-    const int c = threadIdx.x;
-    partial[(int64_t)(c0 + c) * gridDim.x + blockIdx.x] =
-        ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-  }
+  __shared__ double red[kPcgThreads / 64][kColTile];
+  const bool mine = threadIdx.x < kColTile && ((live >> threadIdx.x) & 1u);
+  const double t = tile_sum<kPcgThreads>(acc, red, mine);
+  if (mine) partial[(int64_t)(c0 + threadIdx.x) * gridDim.x + blockIdx.x] = t;
 }
 
 // k_pcg_init per column: x = 0, r = b, partials of b.b; every column's state is re-armed
@@ -444,8 +420,8 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_init(const double* __rest
                                                             int64_t n, int k,
                                                             double* __restrict__ partial,
                                                             int32_t* st, int32_t* flags) {
-  const int c0 = blockIdx.y * kPcgCT;
-  const int nc = min(kPcgCT, k - c0);
+  const int c0 = blockIdx.y * kColTile;
+  const int nc = min(kColTile, k - c0);
   if (blockIdx.x == 0) {
     if (threadIdx.x < nc) {
       *col_done(st, c0 + threadIdx.x) = 0;
@@ -458,16 +434,16 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_init(const double* __rest
       flags[0] = 0;
     }
   }
-  double acc[kPcgCT];
+  double acc[kColTile];
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c) acc[c] = 0.0;
+  for (int c = 0; c < kColTile; ++c) acc[c] = 0.0;
   for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kPcgThreads) {
     const double* b = B + i * ldb + c0;
     double* x = X + i * ldx + c0;
     double* r = R + i * (int64_t)k + c0;
 #pragma unroll
-    for (int c = 0; c < kPcgCT; ++c) {
+    for (int c = 0; c < kColTile; ++c) {
       if (c < nc) {
         const double v = b[c];
         x[c] = 0.0;
@@ -496,18 +472,18 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_dot(const double* __restr
                                                            int64_t n, int k,
                                                            double* __restrict__ partial,
                                                            const int32_t* st) {
-  const int c0 = blockIdx.y * kPcgCT;
-  const unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  const int c0 = blockIdx.y * kColTile;
+  const unsigned live = tile_live(st, c0, min(kColTile, k - c0));
   if (!live) return;
-  double acc[kPcgCT];
+  double acc[kColTile];
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c) acc[c] = 0.0;
+  for (int c = 0; c < kColTile; ++c) acc[c] = 0.0;
   for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kPcgThreads) {
     const double* u = U + i * (int64_t)k + c0;
     const double* v = V + i * (int64_t)k + c0;
 #pragma unroll
-    for (int c = 0; c < kPcgCT; ++c)
+    for (int c = 0; c < kColTile; ++c)
       if ((live >> c) & 1u) acc[c] += u[c] * v[c];
   }
   tile_partials(acc, live, c0, partial);
@@ -516,10 +492,10 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_dot(const double* __restr
 // the totals of the tile's live columns, by the workgroup's four waves (two columns each), left
 // in tot[]; ends with a barrier
 __device__ __forceinline__ void tile_totals(const double* __restrict__ partial, int nb, int c0,
-                                            unsigned live, double (&tot)[kPcgCT]) {
+                                            unsigned live, double (&tot)[kColTile]) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-  for (int u = 0; u < kPcgCT / 4; ++u) {
+  for (int u = 0; u < kColTile / 4; ++u) {
     const int c = w + 4 * u;
     if ((live >> c) & 1u) {
       const double t = col_total(partial + (int64_t)(c0 + c) * nb, nb, lane);
@@ -539,13 +515,13 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_update(double* __restrict
                                                               double* __restrict__ partial,
                                                               int32_t* st, int32_t* flags,
                                                               int it) {
-  __shared__ double tot[kPcgCT];
-  __shared__ double al[kPcgCT];
-  const int c0 = blockIdx.y * kPcgCT;
-  unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  __shared__ double tot[kColTile];
+  __shared__ double al[kColTile];
+  const int c0 = blockIdx.y * kColTile;
+  unsigned live = tile_live(st, c0, min(kColTile, k - c0));
   if (!live) return;
   tile_totals(pq, gridDim.x, c0, live, tot);
-  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
+  if (threadIdx.x < kColTile && ((live >> threadIdx.x) & 1u)) {
     const int c = threadIdx.x;
     const double t = tot[c];
     const double alpha = sc[8 * (c0 + c) + 6 + (it & 1)] / t;
@@ -560,12 +536,12 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_update(double* __restrict
   }
   __syncthreads();
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c)
+  for (int c = 0; c < kColTile; ++c)
     if (((live >> c) & 1u) && !(tot[c] > 0.0)) live &= ~(1u << c);
   if (!live) return;
-  double alpha[kPcgCT], acc[kPcgCT];
+  double alpha[kColTile], acc[kColTile];
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c) {
+  for (int c = 0; c < kColTile; ++c) {
     alpha[c] = ((live >> c) & 1u) ? al[c] : 0.0;
     acc[c] = 0.0;
   }
@@ -576,7 +552,7 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_update(double* __restrict
     const double* p = P + i * (int64_t)k + c0;
     const double* q = Q + i * (int64_t)k + c0;
 #pragma unroll
-    for (int c = 0; c < kPcgCT; ++c) {
+    for (int c = 0; c < kColTile; ++c) {
       if ((live >> c) & 1u) {
         x[c] += alpha[c] * p[c];
         const double v = r[c] - alpha[c] * q[c];
@@ -616,13 +592,13 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_p(const double* __restric
                                                          const double* __restrict__ rz,
                                                          double* sc, int32_t* st, int32_t* flags,
                                                          int first, int it) {
-  __shared__ double tot[kPcgCT];
-  __shared__ double be[kPcgCT];
-  const int c0 = blockIdx.y * kPcgCT;
-  unsigned live = tile_live(st, c0, min(kPcgCT, k - c0));
+  __shared__ double tot[kColTile];
+  __shared__ double be[kColTile];
+  const int c0 = blockIdx.y * kColTile;
+  unsigned live = tile_live(st, c0, min(kColTile, k - c0));
   if (!live) return;
   tile_totals(rz, gridDim.x, c0, live, tot);
-  if (threadIdx.x < kPcgCT && ((live >> threadIdx.x) & 1u)) {
+  if (threadIdx.x < kColTile && ((live >> threadIdx.x) & 1u)) {
     const int c = threadIdx.x;
     double* s = sc + 8 * (c0 + c);
     const double t = tot[c];
@@ -640,18 +616,18 @@ __global__ __launch_bounds__(kPcgThreads) void k_pcgmv_p(const double* __restric
   }
   __syncthreads();
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c)
+  for (int c = 0; c < kColTile; ++c)
     if (((live >> c) & 1u) && !(tot[c] > 0.0)) live &= ~(1u << c);
   if (!live) return;
-  double beta[kPcgCT];
+  double beta[kColTile];
 #pragma unroll
-  for (int c = 0; c < kPcgCT; ++c) beta[c] = ((live >> c) & 1u) ? be[c] : 0.0;
+  for (int c = 0; c < kColTile; ++c) beta[c] = ((live >> c) & 1u) ? be[c] : 0.0;
   for (int64_t i = blockIdx.x * (int64_t)kPcgThreads + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * kPcgThreads) {
     const double* z = Z + i * (int64_t)k + c0;
     double* p = P + i * (int64_t)k + c0;
 #pragma unroll
-    for (int c = 0; c < kPcgCT; ++c)
+    for (int c = 0; c < kColTile; ++c)
       if ((live >> c) & 1u) p[c] = z[c] + beta[c] * p[c];
   }
 }
@@ -704,7 +680,7 @@ static int pcg_mv_workspace(mlamg_pcg* C, int k, hipStream_t s) {
 static int pcg_iteration_mv(mlamg_pcg* C, double* X, int64_t ldx, int k, int it, hipStream_t s) {
   const int nb = C->nb;
   const int64_t n = C->n;
-  const dim3 g(nb, (k + kPcgCT - 1) / kPcgCT), t(kPcgThreads);
+  const dim3 g(nb, (k + kColTile - 1) / kColTile), t(kPcgThreads);
   double* pa = C->mv_partial;                                       // p.q, then r.z partials
   double* pb = C->mv_partial + (size_t)MLAMG_MV_MAX * kPcgMaxBlocks;  // r.r partials
   int32_t* st = C->mv_state;
@@ -729,7 +705,7 @@ int pcg_solve_mv_impl(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int
   MLAMG_TRY(pcg_mv_workspace(C, k, s));
   const int nb = C->nb;
   const int64_t n = C->n;
-  const dim3 g(nb, (k + kPcgCT - 1) / kPcgCT), t(kPcgThreads);
+  const dim3 g(nb, (k + kColTile - 1) / kColTile), t(kPcgThreads);
   int32_t* st = C->mv_state;
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   MLAMG_HIP(hipStreamIsCapturing(s, &cap));
@@ -784,7 +760,7 @@ int mlamg_pcg_create(const mlamg_csr* A, mlamg_hier* M, double rtol, int maxit,
   C->n = A->n_rows;
   C->rtol = rtol;
   C->maxit = maxit;
-  C->nb = pcg_grid(C->n);
+  C->nb = reduce_grid(C->n, kPcgThreads, kPcgMaxBlocks);
   const size_t vec = ((sizeof(double) * (size_t)std::max<int64_t>(C->n, 1)) + 255) & ~size_t(255);
   const size_t total = 3 * vec + 2 * sizeof(double) * kPcgMaxBlocks + 256 + 256;
   if (hipMalloc(&C->mem, total) != hipSuccess) {

@@ -14,24 +14,11 @@
 // blocks G..511, which own no rows in any segment, are not launched: the total adds +0.0 in their
 // position. So every segment's result is bitwise the single call on that segment's rows.
 #include "common.hpp"
+#include "reduce.hpp"
 
 namespace mlamg {
 
 namespace {
-
-constexpr int kSegCT = 8;            // spmm.hip kMvCT
-constexpr int kSegNormBlocks = 1024; // spmm.hip kNormBlocksMv
-constexpr int kSegMeanBlocks = 512;  // spmm.hip kMeanBlocksMv
-
-__device__ __forceinline__ double wave_sum_seg(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ int seg_norm_blocks(int64_t ns) {
-  return (int)min((int64_t)kSegNormBlocks, max((int64_t)1, (ns + 255) / 256));
-}
 
 // k_colsum_partial of segment blockIdx.z on the columns [8 blockIdx.y, 8 blockIdx.y + 8);
 // partial[((seg * k + col) * G) + b], G = gridDim.x
@@ -40,14 +27,14 @@ __global__ __launch_bounds__(256) void k_seg_colsum_partial(const double* __rest
                                                             int64_t ldx, int k,
                                                             const int64_t* __restrict__ off,
                                                             double* __restrict__ partial) {
-  __shared__ double red[4][kSegCT];
+  __shared__ double red[4][kColTile];
   const int seg = blockIdx.z;
   const int64_t r0 = off[seg], ns = off[seg + 1] - r0;
   const int G = gridDim.x;
-  const int nbs = SQ ? min(seg_norm_blocks(ns), G) : kSegMeanBlocks;
+  const int nbs = SQ ? min(reduce_grid(ns, 256, kNormGridCap), G) : kSumGrid;
   if ((int)blockIdx.x >= nbs) return;
-  const int c0 = blockIdx.y * kSegCT;
-  const int nc = min(kSegCT, k - c0);
+  const int c0 = blockIdx.y * kColTile;
+  const int nc = min(kColTile, k - c0);
   double* out = partial + ((int64_t)seg * k + c0) * G + blockIdx.x;
   if constexpr (!SQ) {
     if (blockIdx.x * 256ll >= ns) {
@@ -56,13 +43,13 @@ __global__ __launch_bounds__(256) void k_seg_colsum_partial(const double* __rest
       return;
     }
   }
-  double acc[kSegCT];
+  double acc[kColTile];
 #pragma unroll
-  for (int c = 0; c < kSegCT; ++c) acc[c] = 0.0;
+  for (int c = 0; c < kColTile; ++c) acc[c] = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < ns; i += (int64_t)nbs * 256) {
     const double* p = X + (r0 + i) * ldx + c0;
 #pragma unroll
-    for (int c = 0; c < kSegCT; ++c) {
+    for (int c = 0; c < kColTile; ++c) {
       if (c < nc) {
         const double v = p[c];
         if constexpr (SQ) {
@@ -73,23 +60,9 @@ __global__ __launch_bounds__(256) void k_seg_colsum_partial(const double* __rest
       }
     }
   }
-#pragma unroll
-  for (int c = 0; c < kSegCT; ++c) {
-    const double w = wave_sum_seg(acc[c]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = w;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < nc) {
-    const int c = threadIdx.x;
-    double t;
-    if constexpr (SQ) {
-      t = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    } else {
-      t = 0.0;
-      for (int i = 0; i < 4; ++i) t += red[i][c];
-    }
-    out[(int64_t)c * G] = t;
-  }
+  const bool mine = (int)threadIdx.x < nc;
+  const double t = tile_sum<256>(acc, red, mine);
+  if (mine) out[(int64_t)threadIdx.x * G] = t;
 }
 
 // k_colsum_sqrt of (column blockIdx.x, segment blockIdx.y)
@@ -99,17 +72,10 @@ __global__ __launch_bounds__(1024) void k_seg_colsum_sqrt(const double* __restri
                                                           double* __restrict__ out) {
   __shared__ double red[16];
   const int seg = blockIdx.y;
-  const int nbs = min(seg_norm_blocks(off[seg + 1] - off[seg]), G);
+  const int nbs = min(reduce_grid(off[seg + 1] - off[seg], 256, kNormGridCap), G);
   const double* p = partial + ((int64_t)seg * k + blockIdx.x) * G;
-  double s = strided_sum(p, nbs, threadIdx.x, 1024);
-  s = wave_sum_seg(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    out[(int64_t)seg * k + blockIdx.x] = sqrt(t);
-  }
+  const double t = partials_total<1024>(p, nbs, red);
+  if (threadIdx.x == 0) out[(int64_t)seg * k + blockIdx.x] = sqrt(t);
 }
 
 // k_coltotal of (column blockIdx.x, segment blockIdx.y): thread t adds partials t and t + 256 of
@@ -120,15 +86,9 @@ __global__ __launch_bounds__(256) void k_seg_coltotal(const double* __restrict__
   const int seg = blockIdx.y;
   const double* p = partial + ((int64_t)seg * k + blockIdx.x) * G;
   double s = 0.0;
-  for (int i = threadIdx.x; i < kSegMeanBlocks; i += 256) s += i < G ? p[i] : 0.0;
-  s = wave_sum_seg(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 4; ++i) t += red[i];
-    out[(int64_t)seg * k + blockIdx.x] = t;
-  }
+  for (int i = threadIdx.x; i < kSumGrid; i += 256) s += i < G ? p[i] : 0.0;
+  s = block_sum<256>(s, red);
+  if (threadIdx.x == 0) out[(int64_t)seg * k + blockIdx.x] = s;
 }
 
 // k_colsub_mean of segment blockIdx.y
@@ -165,12 +125,12 @@ int mlamg_norm2_seg_mv(const double* X, int64_t ldx, int k, const int64_t* seg_o
   MLAMG_REQUIRE(nb >= 1 && nb <= kSegMaxSegments, "nb must be in [1, 65535]");
   MLAMG_REQUIRE(max_len >= 0, "max_len < 0");
   hipStream_t s = S(stream);
-  const int G = (int)std::min<int64_t>(kSegNormBlocks, std::max<int64_t>(1, (max_len + 255) / 256));
+  const int G = reduce_grid(max_len, 256, kNormGridCap);
   double* partial =
       static_cast<double*>(scratch(sizeof(double) * (size_t)nb * (size_t)k * (size_t)G, 17));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
   hipLaunchKernelGGL(k_seg_colsum_partial<true>,
-                     dim3(G, (k + kSegCT - 1) / kSegCT, (unsigned)nb), dim3(256), 0, s, X, ldx, k,
+                     dim3(G, (k + kColTile - 1) / kColTile, (unsigned)nb), dim3(256), 0, s, X, ldx, k,
                      seg_offsets, partial);
   hipLaunchKernelGGL(k_seg_colsum_sqrt, dim3(k, (unsigned)nb), dim3(1024), 0, s, partial, G, k,
                      seg_offsets, out);
@@ -188,13 +148,13 @@ int mlamg_remove_mean_seg_mv(double* X, int64_t ldx, int k, const int64_t* seg_o
   MLAMG_REQUIRE(max_len >= 0, "max_len < 0");
   if (max_len == 0) return MLAMG_OK;
   hipStream_t s = S(stream);
-  const int G = (int)std::min<int64_t>(kSegMeanBlocks, (max_len + 255) / 256);
+  const int G = reduce_grid(max_len, 256, kSumGrid);  // max_len >= 1 here
   double* partial = static_cast<double*>(
       scratch(sizeof(double) * (size_t)nb * (size_t)k * (size_t)(G + 1), 18));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
   double* total = partial + (size_t)nb * (size_t)k * (size_t)G;
   hipLaunchKernelGGL(k_seg_colsum_partial<false>,
-                     dim3(G, (k + kSegCT - 1) / kSegCT, (unsigned)nb), dim3(256), 0, s, X, ldx, k,
+                     dim3(G, (k + kColTile - 1) / kColTile, (unsigned)nb), dim3(256), 0, s, X, ldx, k,
                      seg_offsets, partial);
   hipLaunchKernelGGL(k_seg_coltotal, dim3(k, (unsigned)nb), dim3(256), 0, s, partial, G, k, total);
   hipLaunchKernelGGL(k_seg_colsub_mean, dim3((unsigned)((max_len * k + 255) / 256), (unsigned)nb),

@@ -17,6 +17,7 @@
 //    which emits A's stored order without the diagonal, then the diagonal. Both orders matter
 //    downstream (they are the summation orders of the next product) and are reproduced here.
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <chrono>
 #include <cstdio>
@@ -553,7 +554,7 @@ __global__ __launch_bounds__(512) void k_dense_rows(const int32_t* __restrict__ 
     row[j] = v;
     c += v != 0.0;
   }
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  c = wave_sum(c);
   if ((t & 63) == 0) cnt[t >> 6] = c;
   __syncthreads();
   if (t == 0) {

@@ -17,6 +17,7 @@
 // aligned pointers and even leading dimensions (VEC); otherwise the same kernel runs with 8-byte
 // accesses.
 #include "common.hpp"
+#include "reduce.hpp"
 #include "spmm_epi.hpp"
 
 #include <hip/hip_runtime.h>
@@ -229,15 +230,6 @@ int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ld
 }
 
 // ---------------------------------------------------------------- per-column norms
-constexpr int kMvCT = 8;  // columns a thread carries in the reductions below
-constexpr int kNormBlocksMv = 1024;
-
-__device__ __forceinline__ double wave_sum_mv(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // k_sumsq_partial (SQ) / k_ls_sum (!SQ) on the columns [8 blockIdx.y, 8 blockIdx.y + 8): thread t
 // of block b walks the rows b*256 + t + m*gridDim.x*256 exactly as the single-vector kernel
 // does, with one accumulator per column; partial[col * gridDim.x + b]
@@ -245,16 +237,16 @@ template <bool SQ>
 __global__ __launch_bounds__(256) void k_colsum_partial(const double* __restrict__ X, int64_t ldx,
                                                         int64_t n, int k,
                                                         double* __restrict__ partial) {
-  __shared__ double red[4][kMvCT];
-  const int c0 = blockIdx.y * kMvCT;
-  const int nc = min(kMvCT, k - c0);
-  double acc[kMvCT];
+  __shared__ double red[4][kColTile];
+  const int c0 = blockIdx.y * kColTile;
+  const int nc = min(kColTile, k - c0);
+  double acc[kColTile];
 #pragma unroll
-  for (int c = 0; c < kMvCT; ++c) acc[c] = 0.0;
+  for (int c = 0; c < kColTile; ++c) acc[c] = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const double* p = X + i * ldx + c0;
 #pragma unroll
-    for (int c = 0; c < kMvCT; ++c) {
+    for (int c = 0; c < kColTile; ++c) {
       if (c < nc) {
         const double v = p[c];
         if constexpr (SQ) {
@@ -265,23 +257,9 @@ __global__ __launch_bounds__(256) void k_colsum_partial(const double* __restrict
       }
     }
   }
-#pragma unroll
-  for (int c = 0; c < kMvCT; ++c) {
-    const double w = wave_sum_mv(acc[c]);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < nc) {
-    const int c = threadIdx.x;
-    double t;
-    if constexpr (SQ) {
-      t = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-    } else {
-      t = 0.0;
-      for (int i = 0; i < 4; ++i) t += red[i][c];
-    }
-    partial[(int64_t)(c0 + c) * gridDim.x + blockIdx.x] = t;
-  }
+  const bool mine = (int)threadIdx.x < nc;
+  const double t = tile_sum<256>(acc, red, mine);
+  if (mine) partial[(int64_t)(c0 + threadIdx.x) * gridDim.x + blockIdx.x] = t;
 }
 
 // k_sum_sqrt per column: block j sums column j's nb partials and writes sqrt to out[j]
@@ -289,23 +267,16 @@ __global__ __launch_bounds__(1024) void k_colsum_sqrt(const double* __restrict__
                                                       double* __restrict__ out) {
   __shared__ double red[16];
   const double* p = partial + (int64_t)blockIdx.x * nb;
-  double s = strided_sum(p, nb, threadIdx.x, 1024);
-  s = wave_sum_mv(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    out[blockIdx.x] = sqrt(t);
-  }
+  const double t = partials_total<1024>(p, nb, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = sqrt(t);
 }
 
 int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStream_t s) {
   double* partial =
-      static_cast<double*>(scratch(sizeof(double) * kNormBlocksMv * MLAMG_MV_MAX, 8));
+      static_cast<double*>(scratch(sizeof(double) * kNormGridCap * MLAMG_MV_MAX, 8));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
-  const int nb = (int)std::min<int64_t>(kNormBlocksMv, std::max<int64_t>(1, (n + 255) / 256));
-  hipLaunchKernelGGL(k_colsum_partial<true>, dim3(nb, (k + kMvCT - 1) / kMvCT), dim3(256), 0, s, X,
+  const int nb = reduce_grid(n, 256, kNormGridCap);
+  hipLaunchKernelGGL(k_colsum_partial<true>, dim3(nb, (k + kColTile - 1) / kColTile), dim3(256), 0, s, X,
                      ldx, n, k, partial);
   hipLaunchKernelGGL(k_colsum_sqrt, dim3(k), dim3(1024), 0, s, partial, nb, out);
   MLAMG_HIP(hipGetLastError());
@@ -313,22 +284,13 @@ int norm2_mv(const double* X, int64_t ldx, int64_t n, int k, double* out, hipStr
 }
 
 // ---------------------------------------------------------------- per-column mean removal
-constexpr int kMeanBlocksMv = 512;  // lsqr.hip kLsqrBlocks: the fixed grid of k_ls_sum
-
 // k_ls_total per column (256 threads over the 512 partials of column blockIdx.x)
 __global__ __launch_bounds__(256) void k_coltotal(const double* __restrict__ partial,
                                                   double* __restrict__ out) {
   __shared__ double red[4];
-  const double* p = partial + (int64_t)blockIdx.x * kMeanBlocksMv;
-  double s = strided_sum(p, kMeanBlocksMv, threadIdx.x, 256);
-  s = wave_sum_mv(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 4; ++i) t += red[i];
-    out[blockIdx.x] = t;
-  }
+  const double* p = partial + (int64_t)blockIdx.x * kSumGrid;
+  const double t = partials_total<256>(p, kSumGrid, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = t;
 }
 
 // k_ls_sub_mean per column
@@ -345,10 +307,10 @@ __global__ __launch_bounds__(256) void k_colsub_mean(double* __restrict__ X, int
 int remove_mean_mv(double* X, int64_t ldx, int64_t n, int k, hipStream_t s) {
   if (n == 0) return MLAMG_OK;
   double* partial = static_cast<double*>(
-      scratch(sizeof(double) * (kMeanBlocksMv + 1) * MLAMG_MV_MAX, 9));
+      scratch(sizeof(double) * (kSumGrid + 1) * MLAMG_MV_MAX, 9));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
-  double* total = partial + (int64_t)kMeanBlocksMv * MLAMG_MV_MAX;
-  hipLaunchKernelGGL(k_colsum_partial<false>, dim3(kMeanBlocksMv, (k + kMvCT - 1) / kMvCT),
+  double* total = partial + (int64_t)kSumGrid * MLAMG_MV_MAX;
+  hipLaunchKernelGGL(k_colsum_partial<false>, dim3(kSumGrid, (k + kColTile - 1) / kColTile),
                      dim3(256), 0, s, X, ldx, n, k, partial);
   hipLaunchKernelGGL(k_coltotal, dim3(k), dim3(256), 0, s, partial, total);
   hipLaunchKernelGGL(k_colsub_mean, dim3((unsigned)((n * k + 255) / 256)), dim3(256), 0, s, X, ldx,
@@ -372,11 +334,11 @@ __global__ __launch_bounds__(256) void k_gemv_mv(const double* __restrict__ M, i
   if (row >= n || (done && *done)) return;
   const double* r = M + row * n;
   const int64_t j0 = MODE == 2 ? row : 0, j1 = MODE == 1 ? row + 1 : n;
-  for (int c0 = 0; c0 < k; c0 += kMvCT) {
-    const int nc = min(kMvCT, k - c0);
-    double s[kMvCT];
+  for (int c0 = 0; c0 < k; c0 += kColTile) {
+    const int nc = min(kColTile, k - c0);
+    double s[kColTile];
 #pragma unroll
-    for (int c = 0; c < kMvCT; ++c) s[c] = 0.0;
+    for (int c = 0; c < kColTile; ++c) s[c] = 0.0;
     for (int64_t j = j0 + lane; j < j1; j += 8 * 64) {
       double m[8];
 #pragma unroll
@@ -389,20 +351,19 @@ __global__ __launch_bounds__(256) void k_gemv_mv(const double* __restrict__ M, i
         const int64_t q = j + u * 64;
         const double* bp = B + q * ldb + c0;
 #pragma unroll
-        for (int c = 0; c < kMvCT; ++c) {
+        for (int c = 0; c < kColTile; ++c) {
           const double v = (q < j1 && c < nc) ? bp[c] : 0.0;
           s[c] += m[u] * v;
         }
       }
     }
 #pragma unroll
-    for (int c = 0; c < kMvCT; ++c) {
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) s[c] += __shfl_xor(s[c], off, 64);
+    for (int c = 0; c < kColTile; ++c) {
+      s[c] = wave_sum(s[c]);
     }
     if (lane == 0) {
 #pragma unroll
-      for (int c = 0; c < kMvCT; ++c)
+      for (int c = 0; c < kColTile; ++c)
         if (c < nc) Xo[row * ldx + c0 + c] = s[c];
     }
   }

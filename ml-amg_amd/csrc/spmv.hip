@@ -17,6 +17,7 @@
 // extra vector the epilogue reads/writes), SURVEY.md §8(d).
 // The storage formats these kernels read are built in formats.hip; formats.hpp is the seam.
 #include "formats.hpp"
+#include "reduce.hpp"
 
 #include <cstdlib>
 
@@ -125,12 +126,6 @@ __device__ __forceinline__ double epilogue(int row, double s, const Epi& e) {
   return epi_store<OP>(row, s, epi_load<OP>(row, e), e);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // XCD-aware block order: the dispatcher deals blocks round-robin over the 8 XCDs (b % 8 share
 // one L2), so logical block = contiguous chunk per XCD. Neighbouring row blocks then share x
 // lines in the same L2 (7-point stencil: rows i +- 1, +- n, +- n^2). Bijective for any nb.
@@ -225,14 +220,8 @@ __global__ __launch_bounds__(kThreads) void k_csr_stream(const int32_t* __restri
   }
   if constexpr (NORM) {
     // fixed-order block reduction -> deterministic partials
-    double w = wave_sum(sq);
-    if ((tid & 63) == 0) red[tid >> 6] = w;
-    __syncthreads();
-    if (tid == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-      ep.partial[b] = t;
-    }
+    const double t = block_sum<kThreads>(sq, red);
+    if (tid == 0) ep.partial[b] = t;
   }
 }
 
@@ -244,15 +233,8 @@ __global__ __launch_bounds__(1024) void k_finalize_norm(const double* __restrict
                                                         double tol) {
   __shared__ double red[16];
   if (done && *done) return;
-  const int tid = threadIdx.x;
-  double s = 0.0;
-  s = strided_sum(partial, n, tid, 1024);
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
-  if (tid == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
+  const double t = partials_total<1024>(partial, n, red);
+  if (threadIdx.x == 0) {
     const double nrm = sqrt(t);
     if (out) *out = nrm;
     const int c = counter ? *counter : 0;
@@ -309,14 +291,8 @@ __global__ __launch_bounds__(kThreads) void k_sell(const int64_t* __restrict__ s
     if (srow < n_rows) sq = epi_store<OP>(prow, s, pre, ep);
   }
   if constexpr (NORM) {
-    double w = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-      ep.partial[lb] = t;
-    }
+    const double t = block_sum<kThreads>(sq, red);
+    if (threadIdx.x == 0) ep.partial[lb] = t;
   }
 }
 
@@ -397,14 +373,8 @@ __global__ __launch_bounds__(kThreads) void k_sell_dict(const int64_t* __restric
   for (int q = 0; q < SPW; ++q)
     if (srow[q] < n_rows) sq += epi_store<OP>(row[q], acc[q], pre[q], ep);
   if constexpr (NORM) {
-    double v = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-      ep.partial[lb] = t;
-    }
+    const double t = block_sum<kThreads>(sq, red);
+    if (threadIdx.x == 0) ep.partial[lb] = t;
   }
 }
 
@@ -647,14 +617,8 @@ void k_rowpair(const uint8_t* __restrict__ pid,
     p = p_next;
   }
   if constexpr (NORM) {
-    double v = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-      ep.partial[lb] = t;
-    }
+    const double t = block_sum<kThreads>(sq, red);
+    if (threadIdx.x == 0) ep.partial[lb] = t;
   }
 }
 
@@ -939,14 +903,8 @@ void k_rowpat_uni(
     for (int t = 0; t < NF; ++t) fcur[t] = fnext[t];
   }
   if constexpr (NORM) {
-    double v = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kThreads / 64; ++i) t += red[i];
-      ep.partial[lb] = t;
-    }
+    const double t = block_sum<kThreads>(sq, red);
+    if (threadIdx.x == 0) ep.partial[lb] = t;
   }
 #undef MLAMG_FAR_OFF
 }
@@ -1312,14 +1270,8 @@ __global__ __launch_bounds__(kRpWinNT) void k_rowpair_win(const uint16_t* __rest
   }
   if (live && !(MLAMG_RPW_DBG & 4)) sq = epi_store2<OP>(r, both, s0, s1, u, w, ep);
   if constexpr (NORM) {
-    double v = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double t = 0.0;
-      for (int i = 0; i < NT / 64; ++i) t += red[i];
-      ep.partial[lb] = t;
-    }
+    const double t = block_sum<NT>(sq, red);
+    if (threadIdx.x == 0) ep.partial[lb] = t;
   }
 }
 
@@ -1398,9 +1350,7 @@ __global__ __launch_bounds__(512) void k_csr_vcan(const int32_t* __restrict__ in
     }
   }
 #pragma unroll
-  for (int j = 0; j < J; ++j)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off, 64);
+  for (int j = 0; j < J; ++j) acc[j] = wave_sum(acc[j]);
   if (lane == 0)
 #pragma unroll
     for (int j = 0; j < J; ++j) ws[rloc][p + Q * j] = acc[j];
@@ -1549,9 +1499,7 @@ __global__ __launch_bounds__(kVwThreads) void k_vcan_wave(const int32_t* __restr
       acc[j] = s.e0 + 64 * j + lane < s.lb ? acc[j] + s.v[j] * xv[j] : acc[j];
     if (s.last) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[j] += __shfl_xor(acc[j], off, 64);
+      for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
       if (lane == 0) {
         double r = acc[0];
 #pragma unroll
@@ -1978,14 +1926,8 @@ void k_sorted(const int32_t* __restrict__ indptr,
     }
   }
   if constexpr (NORM) {
-    double v = wave_sum(sq);
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) {
-      double t = 0.0;
-      for (int i = 0; i < kSrtThreads / 64; ++i) t += red[i];
-      ep.partial[b] = t;
-    }
+    const double t = block_sum<kSrtThreads>(sq, red);
+    if (tid == 0) ep.partial[b] = t;
   }
 }
 
@@ -2065,10 +2007,8 @@ __global__ __launch_bounds__(kThreads) void k_csr_long(const int32_t* __restrict
     if (tid == 0) sq += epilogue<OP>(r0, s, ep);
   }
   if constexpr (NORM) {
-    double w = wave_sum(sq);
-    if ((tid & 63) == 0) red[tid >> 6] = w;
-    __syncthreads();
-    if (tid == 0) ep.partial[b] = ((red[0] + red[1]) + red[2]) + red[3];
+    const double t = block_sum<kThreads>(sq, red);
+    if (tid == 0) ep.partial[b] = t;
   }
 }
 

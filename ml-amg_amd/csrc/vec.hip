@@ -5,16 +5,11 @@
 //              the end-of-cycle residual b - A@x is reused by the next pre-smoothing sweep)
 //   scale      x[i] = dinv_w[i]*b[i]    (first sweep from a zero initial guess: 0 + d*(b - A@0))
 #include "common.hpp"
+#include "reduce.hpp"
 
 #include <rocprim/rocprim.hpp>
 
 namespace mlamg {
-
-__device__ __forceinline__ double wave_sum_v(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // pass 1: per-block partial sums of x^2 over a fixed grid (grid-stride, fixed order)
 __global__ __launch_bounds__(256) void k_sumsq_partial(const double* __restrict__ x, int64_t n,
@@ -25,35 +20,23 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(const double* __restrict_
   double s = 0.0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     s += x[i] * x[i];
-  s = wave_sum_v(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+  s = block_sum<256>(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(1024) void k_sum_sqrt(const double* __restrict__ partial, int n,
                                                    double* out, const int32_t* done) {
   __shared__ double red[16];
   if (done && *done) return;
-  double s = 0.0;
-  s = strided_sum(partial, n, threadIdx.x, 1024);
-  s = wave_sum_v(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
-    *out = sqrt(t);
-  }
+  const double t = partials_total<1024>(partial, n, red);
+  if (threadIdx.x == 0) *out = sqrt(t);
 }
-
-constexpr int kNormBlocks = 1024;
 
 int norm2_impl(const double* x, int64_t n, double* out, double* partial, const int32_t* done,
                hipStream_t s) {
-  if (!partial) partial = static_cast<double*>(scratch(sizeof(double) * kNormBlocks, 1));
+  if (!partial) partial = static_cast<double*>(scratch(sizeof(double) * kNormGridCap, 1));
   MLAMG_REQUIRE(partial, "scratch allocation failed");
-  int nb = (int)std::min<int64_t>(kNormBlocks, std::max<int64_t>(1, (n + 255) / 256));
+  int nb = reduce_grid(n, 256, kNormGridCap);
   hipLaunchKernelGGL(k_sumsq_partial, dim3(nb), dim3(256), 0, s, x, n, partial, done);
   hipLaunchKernelGGL(k_sum_sqrt, dim3(1), dim3(1024), 0, s, partial, nb, out, done);
   MLAMG_HIP(hipGetLastError());
@@ -65,13 +48,8 @@ __global__ __launch_bounds__(1024) void k_sum_hist(const double* __restrict__ pa
                                                    double tol) {
   __shared__ double red[16];
   if (done && *done) return;
-  double s = strided_sum(partial, n, threadIdx.x, 1024);
-  s = wave_sum_v(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const double t = partials_total<1024>(partial, n, red);
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 16; ++i) t += red[i];
     const double nrm = sqrt(t);
     const int c = *counter;
     if (hist) hist[c] = nrm;
@@ -82,7 +60,7 @@ __global__ __launch_bounds__(1024) void k_sum_hist(const double* __restrict__ pa
 
 int norm_hist_impl(const double* x, int64_t n, double* partial, double* hist, int32_t* counter,
                    int32_t* done, double tol, hipStream_t s) {
-  const int nb = (int)std::min<int64_t>(kNormBlocks, std::max<int64_t>(1, (n + 255) / 256));
+  const int nb = reduce_grid(n, 256, kNormGridCap);
   hipLaunchKernelGGL(k_sumsq_partial, dim3(nb), dim3(256), 0, s, x, n, partial, done);
   hipLaunchKernelGGL(k_sum_hist, dim3(1), dim3(1024), 0, s, partial, nb, hist, counter, done, tol);
   MLAMG_HIP(hipGetLastError());
@@ -252,7 +230,7 @@ __global__ __launch_bounds__(256) void k_csr_fp(const int32_t* __restrict__ ip,
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < nnz; e += stride)
     h += fp_mix(fp_mix(((uint64_t)e << 32) ^ (uint64_t)(uint32_t)ij[e]) ^
                 (uint64_t)__double_as_longlong(v[e]));
-  for (int o = 32; o > 0; o >>= 1) h += __shfl_xor(h, o);
+  h = wave_sum(h);
   if ((threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)h);
 }
 }  // namespace mlamg
