@@ -475,6 +475,13 @@ int mlamg_gs_sweep_mv(const mlamg_gs* G, double* X, int64_t ldx, const double* B
  * of (G, k): 0 = one launch per level, 1 = one-workgroup walk on the CSR arrays, 2 = one-workgroup
  * walk on the level-ordered packed copy (csrc/gs_mv.hip) */
 int mlamg_gs_mv_path(const mlamg_gs* G, int k, int32_t* path);
+/* which kernel mlamg_gs_sweep runs, decided once at create (csrc/gs_plan.cpp): which = 0 for G's
+ * own schedule, 1 for the backward schedule of a symmetric handle (MLAMG_EINVAL without one).
+ * 0 LEVELS (one launch per level), 1 WORKGROUP (one workgroup on the CSR arrays), 2 WAVE (lanes
+ * share a long row), 3 WRING (long rows, LDS ring), 4 PIPE (packed rows, pipelined), 5 PIPE_LDS
+ * (the same with x in LDS), 6 RING (packed rows, LDS ring), 7 WINDOW (one-wave windowed sweep).
+ * NULL arguments and which outside 0..1 return MLAMG_EINVAL before G is read. */
+int mlamg_gs_path(const mlamg_gs* G, int which, int32_t* path);
 
 /* ---------------------------------------------------------------- coarse direct solve
  * Replaces spla.factorized/splu (multigrid.py:168; MLAMG.py:122): the coarse operator is

@@ -5,6 +5,7 @@
 // setup_mode) and the place of every byte of the arena. Integer work on host threads only: no HIP,
 // no device, no library error state, so it builds and runs on a CPU (tests/host).
 #include "batch_plan.hpp"
+#include "gs_plan.hpp"
 
 #include <sched.h>
 #include <unistd.h>
@@ -458,40 +459,13 @@ std::shared_ptr<Pattern> analyse_pattern(const mlamg_amg2v_problem& P, uint64_t 
   return Sp;
 }
 
-// level schedule of the forward sweep (gs.hip): level(i) = 1 + max level(j) over j < i coupled
-// in either direction; returns the number of levels, *maxoff the most off-diagonals of a row
-int level_schedule(const mlamg_amg2v_problem& P, std::vector<int32_t>& level, int* maxoff) {
-  const int64_t n = P.n;
-  std::vector<int32_t> req(n, 0);
-  level.assign(n, 0);
-  int nlev = 0;
-  *maxoff = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    int32_t lv = req[i];
-    int off = 0;
-    for (int32_t k = P.A_indptr[i]; k < P.A_indptr[i + 1]; ++k) {
-      const int32_t j = P.A_indices[k];
-      if (j < i) lv = std::max(lv, level[j] + 1);
-      if (j != i) ++off;
-    }
-    level[i] = lv;
-    *maxoff = std::max(*maxoff, off);
-    for (int32_t k = P.A_indptr[i]; k < P.A_indptr[i + 1]; ++k) {
-      const int32_t j = P.A_indices[k];
-      if (j > i) req[j] = std::max(req[j], lv + 1);
-    }
-    nlev = std::max(nlev, lv + 1);
-  }
-  return nlev;
-}
-
 // the Gauss-Seidel part of a shape: levels (rows ascending within a level), the sweep variant
 // and its packed rows; `room` is the LDS left for the staging area. False: refused (L.code set)
 bool analyse_sweep(const mlamg_amg2v_problem& P, size_t room, bool no_db, Shape& L) {
   const int64_t n = P.n;
   std::vector<int32_t> level;
-  int maxoff = 0;
-  L.nlev = level_schedule(P, level, &maxoff);
+  int32_t maxoff = 0;  // the forward sweep's level recurrence (gs_plan.hpp)
+  L.nlev = gs_level_schedule(P.A_indptr, P.A_indices, n, false, level, &maxoff);
   if (maxoff > kBMaxK) {
     L.code = MLAMG_EUNSUPPORTED;
     L.err = "amg2v_batch: a row of A has more than 32 off-diagonal entries";

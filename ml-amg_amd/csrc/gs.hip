@@ -53,8 +53,6 @@ __global__ __launch_bounds__(256) void k_gs_level(const int32_t* __restrict__ ip
 // The whole sweep in one workgroup: levels in order, a barrier between consecutive levels
 // (workgroup-scope visibility of the x updates). For operators whose levels are narrow, where
 // one launch per level would make the sweep launch-bound.
-constexpr int kGsBlockMaxLevelRows = 8 * kGsBlock;
-
 template <bool BLK>
 __global__ __launch_bounds__(kGsBlock) void k_gs_block(const int32_t* __restrict__ ip,
                                                        const int32_t* __restrict__ ij,
@@ -83,8 +81,6 @@ __global__ __launch_bounds__(kGsBlock) void k_gs_block(const int32_t* __restrict
 // loaded while this level computes, so a level's critical path is its x gathers, the fold and
 // the barrier.
 constexpr int kGsWaveBlock = 1024;
-constexpr int kGsWaveMaxLPR = 16;  // lanes per row: 8 for rows of <= 64 entries (128 rows per
-                                   // pass), 16 up to 128 entries
 
 template <int EPL>
 struct GsWaveRow {
@@ -303,10 +299,7 @@ __global__ __launch_bounds__(kGsBlock) void k_gs_pipe(const int32_t* __restrict_
 // copies (a copy of a register with a load in flight, or a branch join, makes the compiler wait
 // for every outstanding load: that had put one or two memory round trips on each level's critical
 // path, 2.5 us a level at 1024^2). Same products, same order, same division as gs_row.
-constexpr int kGsRingK = 4;
 constexpr int kGsRingSets = 6;                // levels in flight + 1
-constexpr size_t kGsRingLdsMax = 150 * 1024;  // the ring, its sink slot and the level starts
-constexpr uint32_t kGsRingPad = 0xFFFF, kGsRingLater = 0xFFFE;  // the 16-bit slot codes
 struct GsRingRow {
   int32_t pos;  // unclamped
   bool ok;      // pos inside its level
@@ -431,8 +424,6 @@ __global__ __launch_bounds__(kGsBlock) void k_gs_ring(const int32_t* __restrict_
 // earlier-swept products and the row's first lane folds them in stored order, as k_gs_wave does.
 // A step is up to 1024 / LPR rows of one level (host table); the register sets of NS steps rotate
 // by unrolling. Values go to xl in level order (one scatter after the sweep).
-constexpr int32_t kGsWringPad = -1, kGsWringLater = -2, kGsWringDiag = -3, kGsWringFar = -16;
-constexpr size_t kGsWringLdsMax = 150 * 1024;
 template <int EPL>
 constexpr int gs_wring_sets() {
   return 5;
@@ -573,8 +564,6 @@ __global__ __launch_bounds__(gs_wring_threads<EPL>()) void k_gs_wring(const int2
 // Small systems (n <= kGsLdsMax): the same pipelined walk with x held in LDS for the whole sweep
 // (x loaded once, written back once): a level's gathers and its updates are LDS accesses, so a
 // level costs an LDS round trip and a barrier instead of a global-memory round trip.
-constexpr int kGsLdsMax = 8192;  // 64 KB of x: within the default dynamic-LDS limit
-
 template <int K, bool BLK>
 __global__ __launch_bounds__(kGsBlock) void k_gs_lds(const int32_t* __restrict__ rows,
                                                      const int32_t* __restrict__ lptr,
@@ -631,16 +620,6 @@ constexpr int kGsWinBlock = 512;
 #define MLAMG_GSWIN_LAB 0
 #endif
 constexpr int kGsWinStageU = 4;  // positions per staging thread with all loads in flight
-
-// one staging buffer of cap + 1 positions (the last: the dummy of lanes past a level's end),
-// 16-byte aligned sections: vals (cap+1) x KM | diag | b (doubles) | level starts
-// (cap + 2 int32) | columns (cap+1) x KM (uint16 ring slots), after a 16-byte header (levels,
-// first position, positions)
-__host__ __device__ constexpr int64_t win_a16(int64_t b) { return (b + 15) & ~int64_t(15); }
-__host__ __device__ constexpr int64_t win_buf_bytes(int64_t cap, int KM) {
-  return 16 + win_a16(8 * (cap + 1) * KM) + 2 * win_a16(8 * (cap + 1)) + win_a16(4 * (cap + 2)) +
-         win_a16(2 * (cap + 1) * KM);
-}
 
 template <int KM>
 struct WinBuf {
@@ -872,19 +851,14 @@ __global__ void k_gs_b_level(const int32_t* __restrict__ rows, int64_t n,
   if (p < n) blvl[p] = b[rows[p]];
 }
 
-// MLAMG_GS_NO_LDS=1 keeps small systems on the global-memory kernel (A/B runs, tests)
-static bool gs_lds_disabled() {
-  const char* e = std::getenv("MLAMG_GS_NO_LDS");
-  return e && e[0] == '1';
-}
-
+// R = 1, n <= kGsLdsMax (PIPE_LDS): x held in LDS for the whole sweep
 template <int R, int K, bool BLK>
 static void launch_gs_pipe(const mlamg_gs* G, double* x, const double* b, int iterations,
                            const int32_t* done, hipStream_t s) {
   const int64_t n = G->A->n_rows;
   hipLaunchKernelGGL(k_gs_b_level, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, G->rows,
                      n, b, G->b_lvl, done);
-  if (R == 1 && n <= kGsLdsMax && !gs_lds_disabled()) {
+  if (G->path == kGsPathPipeLds) {
     hipLaunchKernelGGL((k_gs_lds<K, BLK>), dim3(1), dim3(kGsBlock), sizeof(double) * n, s, G->rows,
                        G->d_level_ptr, G->n_levels, n, G->pk_col, G->pk_val, G->pk_diag,
                        G->b_lvl, iterations, x, done);
@@ -918,26 +892,6 @@ __global__ void k_gs_win_prep(const int32_t* __restrict__ rows, int64_t n,
   }
 }
 
-static bool gs_ring_disabled() {  // MLAMG_GS_NO_RING=1: A/B runs, tests
-  const char* e = std::getenv("MLAMG_GS_NO_RING");
-  return e && e[0] == '1';
-}
-
-static bool gs_wave_disabled() {  // MLAMG_GS_NO_WAVE=1: A/B runs, tests
-  const char* e = std::getenv("MLAMG_GS_NO_WAVE");
-  return e && e[0] == '1';
-}
-
-static bool gs_wring_disabled() {  // MLAMG_GS_NO_WRING=1: A/B runs, tests
-  const char* e = std::getenv("MLAMG_GS_NO_WRING");
-  return e && e[0] == '1';
-}
-
-static bool gs_win_disabled() {  // MLAMG_GS_NO_WIN=1: A/B runs, tests
-  const char* e = std::getenv("MLAMG_GS_NO_WIN");
-  return e && e[0] == '1';
-}
-
 template <int KM, int RW, int CW, bool BLK>
 static void launch_gs_win(const mlamg_gs* G, double* x, const double* b, int iterations,
                           const int32_t* done, hipStream_t s) {
@@ -954,128 +908,117 @@ static void launch_gs_win(const mlamg_gs* G, double* x, const double* b, int ite
 
 int64_t gs_rows(const mlamg_gs* G) { return G->A->n_rows; }
 
-static size_t gs_ring_lds(const mlamg_gs* G) {
-  return (sizeof(double) << G->ring_log2_r) + sizeof(double) +
-         sizeof(int32_t) * (G->n_levels + 1);
-}
+using I1 = std::integral_constant<int, 1>;
+using I2 = std::integral_constant<int, 2>;
+using I4 = std::integral_constant<int, 4>;
+using I8 = std::integral_constant<int, 8>;
+using I16 = std::integral_constant<int, 16>;
 
+// the kernel is the plan's (G->path, gs_plan.cpp); here only its template instance is chosen
 template <bool BLK>
 static int gs_sweep_one(const mlamg_gs* G, double* x, const double* b, int iterations,
                         const int32_t* done, hipStream_t s) {
   const mlamg_csr* A = G->A;
-  if (A->n_rows == 0 || iterations <= 0) return MLAMG_OK;
-  const bool pipe = G->pk_k > 0 && G->n_levels > 4;
-  if (pipe && G->win_rw > 0 && !gs_win_disabled()) {
-    // win_rw = 64-row slots per level: up to 4 sweeping waves, then 2 rows per lane
-    if (G->pk_k == 4) {
-      switch (G->win_rw) {
-        case 1: launch_gs_win<4, 1, 1, BLK>(G, x, b, iterations, done, s); break;
-        case 2: launch_gs_win<4, 1, 2, BLK>(G, x, b, iterations, done, s); break;
-        case 3: launch_gs_win<4, 1, 3, BLK>(G, x, b, iterations, done, s); break;
-        case 4: launch_gs_win<4, 1, 4, BLK>(G, x, b, iterations, done, s); break;
-        default: launch_gs_win<4, 2, 4, BLK>(G, x, b, iterations, done, s); break;
+  const int64_t n = A->n_rows;
+  if (n == 0 || iterations <= 0) return MLAMG_OK;
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  switch (G->path) {
+    case kGsPathWindow: {
+      // win_rw = 64-row slots per level: up to 4 sweeping waves, then 2 rows per lane
+      auto go = [&](auto km) {
+        constexpr int KM = decltype(km)::value;
+        switch (G->win_rw) {
+          case 1: launch_gs_win<KM, 1, 1, BLK>(G, x, b, iterations, done, s); break;
+          case 2: launch_gs_win<KM, 1, 2, BLK>(G, x, b, iterations, done, s); break;
+          case 3: launch_gs_win<KM, 1, 3, BLK>(G, x, b, iterations, done, s); break;
+          case 4: launch_gs_win<KM, 1, 4, BLK>(G, x, b, iterations, done, s); break;
+          default: launch_gs_win<KM, 2, 4, BLK>(G, x, b, iterations, done, s); break;
+        }
+      };
+      if (G->pk_k == 4) go(I4());
+      else go(I8());
+      break;
+    }
+    case kGsPathRing:
+      // one sweep per launch pair: the products of the old values are formed before each
+      for (int it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL((k_gs_ring_prep<BLK>), dim3(nb), dim3(256), 0, s, G->rows, n, G->rcol,
+                           G->pk_val, G->pk_diag, b, x, G->rpv, G->b_lvl, done);
+        hipLaunchKernelGGL((k_gs_ring<BLK>), dim3(1), dim3(kGsBlock), G->ring_lds, s,
+                           G->d_level_ptr, G->n_levels, reinterpret_cast<const uint2*>(G->rcode),
+                           G->rpv, G->pk_diag, G->b_lvl, G->ring_log2_r, G->rxl, done);
+        // the level-ordered values back to x (coalesced stores in the sweep, one scatter here)
+        hipLaunchKernelGGL(k_gs_win_post, dim3(nb), dim3(256), 0, s, G->rows, n, G->rxl, x, done);
       }
-    } else {
-      switch (G->win_rw) {
-        case 1: launch_gs_win<8, 1, 1, BLK>(G, x, b, iterations, done, s); break;
-        case 2: launch_gs_win<8, 1, 2, BLK>(G, x, b, iterations, done, s); break;
-        case 3: launch_gs_win<8, 1, 3, BLK>(G, x, b, iterations, done, s); break;
-        case 4: launch_gs_win<8, 1, 4, BLK>(G, x, b, iterations, done, s); break;
-        default: launch_gs_win<8, 2, 4, BLK>(G, x, b, iterations, done, s); break;
-      }
-    }
-  } else if (pipe && G->rcol && G->rpv && G->rcode && G->rxl && !gs_ring_disabled() &&
-             gs_ring_lds(G) <= kGsRingLdsMax) {
-    const int64_t n = A->n_rows;
-    // one sweep per launch pair: the products of the old values are formed before each
-    for (int it = 0; it < iterations; ++it) {
-      hipLaunchKernelGGL((k_gs_ring_prep<BLK>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                         G->rows, n, G->rcol, G->pk_val, G->pk_diag, b, x, G->rpv, G->b_lvl,
-                         done);
-      hipLaunchKernelGGL((k_gs_ring<BLK>), dim3(1), dim3(kGsBlock), gs_ring_lds(G), s,
-                         G->d_level_ptr, G->n_levels, reinterpret_cast<const uint2*>(G->rcode),
-                         G->rpv, G->pk_diag, G->b_lvl, G->ring_log2_r, G->rxl, done);
-      // the level-ordered values back to x (coalesced stores in the sweep, one scatter here)
-      hipLaunchKernelGGL(k_gs_win_post, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                         G->rows, n, G->rxl, x, done);
-    }
-  } else if (pipe && G->max_level_rows <= 2 * kGsBlock) {
-    const bool one = G->max_level_rows <= kGsBlock;
-    if (G->pk_k == 4) {
-      if (one) launch_gs_pipe<1, 4, BLK>(G, x, b, iterations, done, s);
-      else launch_gs_pipe<2, 4, BLK>(G, x, b, iterations, done, s);
-    } else {
-      if (one) launch_gs_pipe<1, 8, BLK>(G, x, b, iterations, done, s);
-      else launch_gs_pipe<2, 8, BLK>(G, x, b, iterations, done, s);
-    }
-  } else if (G->wr_code && G->rxl && G->b_lvl && !gs_wring_disabled()) {
-    const int64_t n = A->n_rows;
-    const int span = G->wr_lpr * G->wr_epl;
-    auto go = [&](auto l, auto e) {
-      hipLaunchKernelGGL((k_gs_wring<decltype(l)::value, decltype(e)::value, BLK>), dim3(1),
-                         dim3(gs_wring_threads<decltype(e)::value>()), G->wr_lds, s, G->wr_st, G->wr_steps, (int32_t)(n - 1),
-                         G->wr_code, G->wr_pv, G->wr_len, G->b_lvl, G->wr_d, G->wr_log2, G->rxl,
-                         done);
-    };
-    using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>;
-    using I8 = std::integral_constant<int, 8>;
-    using I16 = std::integral_constant<int, 16>;
-    for (int it = 0; it < iterations; ++it) {
-      hipLaunchKernelGGL((k_gs_wring_prep<BLK>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                         s, G->rows, n, A->indptr, A->indices, A->data, G->wr_code, span, b, x,
-                         G->wr_pv, G->b_lvl, G->wr_d, done);
-      if (G->wr_epl == 2) {
-        if (G->wr_lpr == 8) go(I8(), I2());
-        else go(I16(), I2());
+      break;
+    case kGsPathPipe:
+    case kGsPathPipeLds: {
+      const bool one = G->max_level_rows <= kGsBlock;  // rows per thread R = 1, else 2
+      if (G->pk_k == 4) {
+        if (one) launch_gs_pipe<1, 4, BLK>(G, x, b, iterations, done, s);
+        else launch_gs_pipe<2, 4, BLK>(G, x, b, iterations, done, s);
       } else {
-        if (G->wr_lpr == 8) go(I8(), I4());
-        else go(I16(), I4());
+        if (one) launch_gs_pipe<1, 8, BLK>(G, x, b, iterations, done, s);
+        else launch_gs_pipe<2, 8, BLK>(G, x, b, iterations, done, s);
       }
-      hipLaunchKernelGGL(k_gs_win_post, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                         G->rows, n, G->rxl, x, done);
+      break;
     }
-  } else if (G->wpos && G->max_level_rows <= kGsBlockMaxLevelRows && G->n_levels > 4 &&
-             !gs_wave_disabled()) {
-    auto go = [&](auto l, auto e) {
-      hipLaunchKernelGGL((k_gs_wave<decltype(l)::value, decltype(e)::value, BLK>), dim3(1),
-                         dim3(kGsWaveBlock), 0, s, reinterpret_cast<const int4*>(G->wpos),
-                         A->indices, A->data, G->d_level_ptr, G->n_levels, iterations, x, b,
-                         done);
-    };
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
-    using I4 = std::integral_constant<int, 4>;
-    using I8 = std::integral_constant<int, 8>;
-    using I16 = std::integral_constant<int, 16>;
-    const int ml = G->max_len;
-    // 8 lanes per row when the levels average more than 64 rows (128 rows per pass: fewer
-    // passes, each with its loads on the critical path), else 16 (fewer entries per lane)
-    static const char* lpr_env = std::getenv("MLAMG_GS_WAVE_LPR");  // A/B knob: 8 or 16
-    const bool wide = lpr_env ? lpr_env[0] == '8' : A->n_rows > 64 * (int64_t)G->n_levels;
-    if (wide && ml <= 64) {
-      if (ml <= 8) go(I8(), I1());
-      else if (ml <= 16) go(I8(), I2());
-      else if (ml <= 32) go(I8(), I4());
-      else go(I8(), I8());
-    } else {
-      if (ml <= 16) go(I16(), I1());
-      else if (ml <= 32) go(I16(), I2());
-      else if (ml <= 64) go(I16(), I4());
-      else go(I16(), I8());
-    }
-  } else if (G->max_level_rows <= kGsBlock && G->n_levels > 4) {
-    // one row per thread per level; wider levels go one launch per level over the whole chip
-    hipLaunchKernelGGL(k_gs_block<BLK>, dim3(1), dim3(kGsBlock), 0, s, A->indptr, A->indices, A->data,
-                       G->rows, G->d_level_ptr, G->n_levels, iterations, x, b, done);
-  } else {
-    for (int it = 0; it < iterations; ++it) {
-      for (int32_t l = 0; l < G->n_levels; ++l) {
-        const int32_t a = G->level_ptr[l], cnt = G->level_ptr[l + 1] - a;
-        hipLaunchKernelGGL(k_gs_level<BLK>, dim3((cnt + 255) / 256), dim3(256), 0, s, A->indptr,
-                           A->indices, A->data, G->rows + a, cnt, x, b, done);
+    case kGsPathWring: {
+      const int span = G->wr_lpr * G->wr_epl;
+      auto go = [&](auto l, auto e) {
+        hipLaunchKernelGGL((k_gs_wring<decltype(l)::value, decltype(e)::value, BLK>), dim3(1),
+                           dim3(gs_wring_threads<decltype(e)::value>()), G->wr_lds, s, G->wr_st, G->wr_steps, (int32_t)(n - 1),
+                           G->wr_code, G->wr_pv, G->wr_len, G->b_lvl, G->wr_d, G->wr_log2, G->rxl,
+                           done);
+      };
+      for (int it = 0; it < iterations; ++it) {
+        hipLaunchKernelGGL((k_gs_wring_prep<BLK>), dim3(nb), dim3(256), 0, s, G->rows, n,
+                           A->indptr, A->indices, A->data, G->wr_code, span, b, x, G->wr_pv,
+                           G->b_lvl, G->wr_d, done);
+        if (G->wr_epl == 2) {
+          if (G->wr_lpr == 8) go(I8(), I2());
+          else go(I16(), I2());
+        } else {
+          if (G->wr_lpr == 8) go(I8(), I4());
+          else go(I16(), I4());
+        }
+        hipLaunchKernelGGL(k_gs_win_post, dim3(nb), dim3(256), 0, s, G->rows, n, G->rxl, x, done);
       }
+      break;
     }
+    case kGsPathWave: {
+      auto go = [&](auto l, auto e) {
+        hipLaunchKernelGGL((k_gs_wave<decltype(l)::value, decltype(e)::value, BLK>), dim3(1),
+                           dim3(kGsWaveBlock), 0, s, reinterpret_cast<const int4*>(G->wpos),
+                           A->indices, A->data, G->d_level_ptr, G->n_levels, iterations, x, b,
+                           done);
+      };
+      auto lanes = [&](auto l) {
+        switch (G->wave_epl) {
+          case 1: go(l, I1()); break;
+          case 2: go(l, I2()); break;
+          case 4: go(l, I4()); break;
+          default: go(l, I8()); break;
+        }
+      };
+      if (G->wave_lpr == 8) lanes(I8());
+      else lanes(I16());
+      break;
+    }
+    case kGsPathWorkgroup:
+      // one row per thread per level; wider levels go one launch per level over the whole chip
+      hipLaunchKernelGGL(k_gs_block<BLK>, dim3(1), dim3(kGsBlock), 0, s, A->indptr, A->indices, A->data,
+                         G->rows, G->d_level_ptr, G->n_levels, iterations, x, b, done);
+      break;
+    case kGsPathLevels:
+      for (int it = 0; it < iterations; ++it) {
+        for (int32_t l = 0; l < G->n_levels; ++l) {
+          const int32_t a = G->level_ptr[l], cnt = G->level_ptr[l + 1] - a;
+          hipLaunchKernelGGL(k_gs_level<BLK>, dim3((cnt + 255) / 256), dim3(256), 0, s, A->indptr,
+                             A->indices, A->data, G->rows + a, cnt, x, b, done);
+        }
+      }
+      break;
   }
   MLAMG_HIP(hipGetLastError());
   return MLAMG_OK;
@@ -1100,230 +1043,106 @@ int gs_sweep_impl(const mlamg_gs* G, double* x, const double* b, int iterations,
 
 using namespace mlamg;
 
-// The ring sweep's plan (levels of <= 1024 rows, K = 4 slots): W = the widest level distance from
-// a row to an earlier-swept column; positions of levels [l - W, l] must fit the ring
-// (<= 8,192 doubles). Optional: rcol stays nullptr otherwise.
-static void setup_ring(mlamg_gs* G, const std::vector<int32_t>& level,
-                       const std::vector<int32_t>& rows, const std::vector<int32_t>& pcol) {
-  const int64_t n = G->A->n_rows;
-  const int K = kGsRingK;
-  if (G->max_level_rows > kGsBlock || G->n_levels <= 4 || n == 0) return;
-  std::vector<int32_t> pos(n);
-  for (int64_t p = 0; p < n; ++p) pos[rows[p]] = (int32_t)p;
-  int W = 0;
-  for (int64_t p = 0; p < n; ++p)
-    for (int k = 0; k < K; ++k) {
-      const int32_t c = pcol[(size_t)p * K + k];
-      if (c >= 0 && level[c] < level[rows[p]]) W = std::max(W, level[rows[p]] - level[c]);
-    }
-  const std::vector<int32_t>& lp = G->level_ptr;
-  int64_t span = 0;
-  for (int l = 0; l < G->n_levels; ++l)
-    span = std::max<int64_t>(span, lp[l + 1] - lp[std::max(0, l - W)]);
-  int lg = 0;
-  while ((int64_t(1) << lg) < span) ++lg;
-  if (lg > 13) return;
-  std::vector<int32_t> rc((size_t)n * K);
-  for (int64_t p = 0; p < n; ++p)
-    for (int k = 0; k < K; ++k) {
-      const int32_t c = pcol[(size_t)p * K + k];
-      rc[(size_t)p * K + k] = c < 0 ? -1 : (level[c] < level[rows[p]] ? pos[c] : -(c + 2));
-    }
-  if (hipMalloc(&G->rcol, sizeof(int32_t) * rc.size()) != hipSuccess) {
-    G->rcol = nullptr;
-    return;
+static_assert(sizeof(GsStep) == sizeof(int2) && offsetof(GsStep, first) == offsetof(int2, x) &&
+                  offsetof(GsStep, rows) == offsetof(int2, y),
+              "k_gs_wring reads the plan's steps as int2");
+
+// frees the handle's device buffers from owned[from] on
+static void gs_release(mlamg_gs* G, size_t from) {
+  for (size_t i = from; i < G->owned.size(); ++i) {
+    (void)hipFree(*G->owned[i]);
+    *G->owned[i] = nullptr;
   }
-  (void)hipMemcpy(G->rcol, rc.data(), sizeof(int32_t) * rc.size(), hipMemcpyHostToDevice);
-  std::vector<uint16_t> code(rc.size());
-  const int32_t RM = (1 << lg) - 1;
-  for (size_t e = 0; e < rc.size(); ++e)
-    code[e] = (uint16_t)(rc[e] >= 0 ? (rc[e] & RM) : (rc[e] == -1 ? kGsRingPad : kGsRingLater));
-  if (hipMalloc(&G->rpv, sizeof(double) * rc.size()) != hipSuccess) G->rpv = nullptr;
-  if (hipMalloc(&G->rxl, sizeof(double) * n) != hipSuccess) G->rxl = nullptr;
-  if (hipMalloc(&G->rcode, sizeof(uint16_t) * code.size()) != hipSuccess) G->rcode = nullptr;
-  else
-    (void)hipMemcpy(G->rcode, code.data(), sizeof(uint16_t) * code.size(), hipMemcpyHostToDevice);
-  G->ring_log2_r = lg;
+  G->owned.resize(from);
 }
 
-// The long-row ring sweep's plan (rows of 9..64 entries, levels swept in steps of 1024 / LPR
-// rows): the slot codes in the padded level order, the row lengths, the step table and the ring
-// (W levels of positions, <= 8,192 slots). Optional: wr_code stays nullptr otherwise.
-static void setup_wring(mlamg_gs* G, const std::vector<int32_t>& ip,
-                        const std::vector<int32_t>& ij, const std::vector<int32_t>& level,
-                        const std::vector<int32_t>& rows) {
-  const int64_t n = G->A->n_rows;
-  const int nlev = G->n_levels;
-  const int ml = G->max_len;
-  if (n == 0 || nlev <= 4 || ml > 64) return;
-  // 8 lanes per row when levels average more than 64 rows, else 16; two slots per lane in
-  // 1024-thread workgroups, four (rows of 33..64 entries, or 17..32 on wide levels) in 512-thread
-  // ones: five register sets of four slots exceed the 128 VGPRs a 1024-thread workgroup has
-  // (spilled, the 3-D 128^3 level-1 sweep ran 2x slower than k_gs_wave)
-  const bool wide = n > 64 * (int64_t)nlev;
-  const int lpr = (wide && ml <= 32) ? 8 : 16;
-  const int epl = ml <= 2 * lpr ? 2 : 4;
-  if (ml > lpr * epl) return;
-  const int span = lpr * epl, rows_per_step = (epl == 2 ? 1024 : 512) / lpr;
-  std::vector<int32_t> pos(n);
-  for (int64_t p = 0; p < n; ++p) pos[rows[p]] = (int32_t)p;
-  int W = 0;
-  for (int64_t i = 0; i < n; ++i)
-    for (int k = ip[i]; k < ip[i + 1]; ++k)
-      if (ij[k] != i && level[ij[k]] < level[i]) W = std::max(W, level[i] - level[ij[k]]);
-  const std::vector<int32_t>& lp = G->level_ptr;
-  std::vector<int2> st;
-  for (int l = 0; l < nlev; ++l)
-    for (int32_t a = lp[l]; a < lp[l + 1]; a += rows_per_step)
-      st.push_back(make_int2(a, std::min<int32_t>(rows_per_step, lp[l + 1] - a)));
-  // a step costs about what one of k_gs_wave's level passes does: levels much wider than a step
-  // stay there (3-D 128^3 level 1, 14 steps a level: V-cycle 63 -> 137 ms through this kernel)
-  if (st.size() > 2 * (size_t)nlev) return;
-  const size_t rest = sizeof(double) * 3 +
-                      (sizeof(double) + sizeof(uint16_t)) * rows_per_step * span + 8 +
-                      sizeof(int2) * st.size() + 16;
-  if (rest >= kGsWringLdsMax) return;
-  int64_t cap = 8192;  // ring slots: at most 8,192 and what the LDS budget leaves
-  while (cap > 1 && rest + sizeof(double) * cap > kGsWringLdsMax) cap >>= 1;
-  // the ring horizon Wr: the most levels back whose positions fit the ring; couplings further
-  // back are read from xl two steps ahead, which needs Wr >= 2 (a step advances <= 1 level)
-  auto span_of = [&](int w) {
-    int64_t sp = 0;
-    for (int l = 0; l < nlev; ++l) sp = std::max<int64_t>(sp, lp[l + 1] - lp[std::max(0, l - w)]);
-    return sp;
-  };
-  int Wr = W;
-  while (Wr > 2 && span_of(Wr) > cap) Wr = std::max(2, Wr * 7 / 8);
-  if (span_of(Wr) > cap || (Wr < W && Wr < 2)) return;
-  const int64_t spanp = span_of(Wr);
-  int lg = 0;
-  while ((int64_t(1) << lg) < spanp) ++lg;
-  if (lg > 13 || (int64_t(1) << lg) > cap) return;
-  const size_t lds = rest + (sizeof(double) << lg);
-  const int32_t RM = (1 << lg) - 1;
-  std::vector<int32_t> code((size_t)n * span, kGsWringPad);
-  std::vector<int32_t> len(n);
-  for (int64_t p = 0; p < n; ++p) {
-    const int32_t i = rows[p];
-    len[p] = ip[i + 1] - ip[i];
-    for (int k = ip[i]; k < ip[i + 1]; ++k) {
-      const int32_t j = ij[k];
-      int32_t c = kGsWringLater;
-      if (j == i) c = kGsWringDiag;
-      else if (level[j] < level[i]) c = level[i] - level[j] <= Wr ? (pos[j] & RM) : kGsWringFar - pos[j];
-      code[(size_t)p * span + (k - ip[i])] = c;
-    }
-  }
-  const size_t m = (size_t)n * span;
-  bool ok = hipMalloc(&G->wr_code, sizeof(int32_t) * m) == hipSuccess;
-  ok = ok && hipMalloc(&G->wr_pv, sizeof(double) * m) == hipSuccess;
-  ok = ok && hipMalloc(&G->wr_len, sizeof(int32_t) * n) == hipSuccess;
-  ok = ok && hipMalloc(&G->wr_d, sizeof(double) * n) == hipSuccess;
-  ok = ok && hipMalloc(&G->wr_st, sizeof(int2) * st.size()) == hipSuccess;
-  if (!G->rxl) ok = ok && hipMalloc(&G->rxl, sizeof(double) * n) == hipSuccess;
-  if (!G->b_lvl) ok = ok && hipMalloc(&G->b_lvl, sizeof(double) * n) == hipSuccess;
-  if (!ok) {
-    for (void* q : {(void*)G->wr_code, (void*)G->wr_pv, (void*)G->wr_len, (void*)G->wr_d,
-                    (void*)G->wr_st})
-      if (q) (void)hipFree(q);
-    G->wr_code = nullptr;
-    G->wr_pv = G->wr_d = nullptr;
-    G->wr_len = nullptr;
-    G->wr_st = nullptr;
-    return;
-  }
-  (void)hipMemcpy(G->wr_code, code.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice);
-  (void)hipMemset(G->wr_pv, 0, sizeof(double) * m);
-  (void)hipMemcpy(G->wr_len, len.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice);
-  (void)hipMemcpy(G->wr_st, st.data(), sizeof(int2) * st.size(), hipMemcpyHostToDevice);
-  G->wr_lpr = lpr;
-  G->wr_epl = epl;
-  G->wr_steps = (int32_t)st.size();
-  G->wr_log2 = lg;
-  G->wr_lds = lds;
-}
-
-// The windowed one-wave sweep's plan: W = the widest level distance of a coupling, chunks of
-// levels that fit a staging buffer, and the ring that holds every position a step and the
-// concurrent staging of the next chunk touch. Optional: win_rw stays 0 when levels are wider
-// than 64 * RW rows or the ring and buffers do not fit the LDS budget.
-static void setup_window(mlamg_gs* G, const std::vector<int32_t>& ip,
-                         const std::vector<int32_t>& ij, const std::vector<int32_t>& level,
-                         const std::vector<int32_t>& rows, const std::vector<int32_t>& pcol,
-                         int K) {
-  const int64_t n = G->A->n_rows;
-  const int nlev = G->n_levels;
-  const int rw = (G->max_level_rows + 63) / 64;  // 64-row slots: <= 4 waves x 2 rows per lane
-  if (rw < 1 || rw > 8 || nlev <= 4) return;
-  int W = 0;
-  for (int64_t i = 0; i < n; ++i)
-    for (int k = ip[i]; k < ip[i + 1]; ++k)
-      if (ij[k] != i) W = std::max(W, std::abs(level[ij[k]] - level[i]));
-  const std::vector<int32_t>& lp = G->level_ptr;
-  const size_t budget = 150 * 1024;
-  for (int cap = 4096; cap >= G->max_level_rows; cap = cap * 7 / 8) {
-    std::vector<int32_t> clev{0};
-    for (int l = 0; l < nlev;) {
-      const int start = l;
-      while (l < nlev && (l == start || lp[l + 1] - lp[start] <= cap)) ++l;
-      clev.push_back(l);
-    }
-    const int nch = (int)clev.size() - 1;
-    int64_t span = 0;
-    for (int ch = 0; ch < nch; ++ch) {
-      const int lo = std::max(0, clev[ch] - W);
-      const int hi = std::min(nlev, clev[std::min(ch + 2, nch)] + W);
-      span = std::max<int64_t>(span, lp[hi] - lp[lo]);
-    }
-    int lg = 0;
-    while ((int64_t(1) << lg) < span) ++lg;
-    const size_t ring = ((size_t(1) << lg) + 4) * 8;
-    const size_t bufs = 2 * (size_t)win_buf_bytes(cap, K);
-    if (ring + bufs > budget) continue;
-    // per chunk: {levels, first position, positions, old-x start} {old-x count, level-start
-    // offset, -, -}, then every chunk's level starts relative to its first position
-    std::vector<int32_t> plan(8 * (size_t)nch);
-    for (int ch = 0; ch < nch; ++ch) {
-      const int l0 = clev[ch], l1 = clev[ch + 1];
-      const int la = ch == 0 ? 0 : std::min(nlev, l0 + W), lb = std::min(nlev, l1 + W);
-      int32_t* d = plan.data() + 8 * (size_t)ch;
-      d[0] = l1 - l0;
-      d[1] = lp[l0];
-      d[2] = lp[l1] - lp[l0];
-      d[3] = lp[la];
-      d[4] = lp[lb] - lp[la];
-      d[5] = (int32_t)plan.size() - 8 * nch;
-      for (int l = l0; l <= l1; ++l) plan.push_back(lp[l] - lp[l0]);
-    }
-    std::vector<int32_t> pos(n), wcol((size_t)n * K, -1);
-    for (int64_t p = 0; p < n; ++p) pos[rows[p]] = (int32_t)p;
-    for (size_t q = 0; q < (size_t)n * K; ++q)
-      if (pcol[q] >= 0) wcol[q] = pos[pcol[q]];
-    if (hipMalloc(&G->wcol, sizeof(int32_t) * std::max<size_t>((size_t)n * K, 1)) != hipSuccess ||
-        hipMalloc(&G->d_clev, sizeof(int32_t) * plan.size()) != hipSuccess ||
-        hipMalloc(&G->win_xl, sizeof(double) * std::max<int64_t>(n, 1)) != hipSuccess) {
-      for (void* q : {(void*)G->wcol, (void*)G->d_clev, (void*)G->win_xl})
-        if (q) (void)hipFree(q);
-      G->wcol = nullptr;
-      G->d_clev = nullptr;
-      G->win_xl = nullptr;
+// Every device buffer of a handle is made here: `count` elements (at least one) for the handle's
+// field, filled from `src` unless nullptr, owned by the handle from then on. After a failure rc
+// is set and further calls do nothing.
+struct GsUpload {
+  mlamg_gs* G;
+  int rc = MLAMG_OK;
+  template <class T, class U = T>
+  void put(T** field, size_t count, const U* src = nullptr) {
+    static_assert(sizeof(T) == sizeof(U), "element sizes differ");
+    if (rc != MLAMG_OK) return;
+    if (hipMalloc(field, sizeof(T) * std::max<size_t>(count, 1)) != hipSuccess) {
+      *field = nullptr;
+      set_error("gs_create: hipMalloc failed");
+      rc = MLAMG_ENOMEM;
       return;
     }
-    (void)hipMemcpy(G->wcol, wcol.data(), sizeof(int32_t) * (size_t)n * K, hipMemcpyHostToDevice);
-    (void)hipMemcpy(G->d_clev, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice);
-    G->win_w = W;
-    G->win_cap = cap;
-    G->ring_log2 = lg;
-    G->n_chunks = nch;
-    G->win_lds = ring + bufs + 64;
-    G->win_rw = rw;
-    return;
+    G->owned.push_back(reinterpret_cast<void**>(field));
+    if (src && count &&
+        hipMemcpy(*field, src, sizeof(T) * count, hipMemcpyHostToDevice) != hipSuccess) {
+      set_error("gs_create: hipMemcpy failed");
+      rc = MLAMG_EHIP;
+    }
   }
+};
+
+// The device side of a plan. rows and the level starts are mandatory; a layout that cannot be
+// allocated or copied gives back what it had got and is dropped from the plan's candidates, and
+// the path is chosen among what is left.
+static int gs_upload(mlamg_gs* G, GsPlan& P) {
+  const size_t n = (size_t)P.n;
+  GsUpload up{G};
+  G->level_ptr = P.level_ptr;
+  up.put(&G->rows, n, P.rows.data());
+  up.put(&G->d_level_ptr, P.level_ptr.size(), P.level_ptr.data());
+  if (up.rc != MLAMG_OK) return up.rc;
+  auto optional = [&](bool& have, auto&& layout) {
+    if (!have) return;
+    const size_t mark = G->owned.size();
+    layout();
+    if (up.rc == MLAMG_OK) return;
+    gs_release(G, mark);
+    up.rc = MLAMG_OK;
+    have = false;
+  };
+  optional(P.packed, [&] {
+    up.put(&G->pk_col, P.pcol.size(), P.pcol.data());
+    up.put(&G->pk_val, P.pval.size(), P.pval.data());
+    up.put(&G->pk_diag, n, P.pdiag.data());
+    up.put(&G->b_lvl, n);
+  });
+  if (P.packed) G->pk_k = P.K;
+  else P.window = P.ring = false;
+  optional(P.window, [&] {
+    up.put(&G->wcol, P.wcol.size(), P.wcol.data());
+    up.put(&G->d_clev, P.clev.size(), P.clev.data());
+    up.put(&G->win_xl, n);
+  });
+  optional(P.ring, [&] {
+    up.put(&G->rcol, P.rcol.size(), P.rcol.data());
+    up.put(&G->rcode, P.rcode.size(), P.rcode.data());
+    up.put(&G->rpv, P.rcol.size());
+    up.put(&G->rxl, n);
+  });
+  optional(P.wave, [&] { up.put(&G->wpos, P.wpos.size(), P.wpos.data()); });
+  optional(P.wring, [&] {
+    up.put(&G->wr_pv, P.wr_code.size());  // pads stay 0: zeroed while the copies below run
+    if (up.rc == MLAMG_OK &&
+        hipMemset(G->wr_pv, 0, sizeof(double) * P.wr_code.size()) != hipSuccess)
+      up.rc = MLAMG_EHIP;
+    up.put(&G->wr_code, P.wr_code.size(), P.wr_code.data());
+    up.put(&G->wr_len, n, P.wr_len.data());
+    up.put(&G->wr_st, P.wr_st.size(), P.wr_st.data());
+    up.put(&G->wr_d, n);
+    up.put(&G->rxl, n);
+    up.put(&G->b_lvl, n);
+  });
+  P.path = gs_select_path(P);
+  static_cast<GsScalars&>(*G) = P;
+  return MLAMG_OK;
 }
 
-// one sweep direction's schedule and packed copies
-static int gs_build(const mlamg_csr* A, bool backward, bool block, mlamg_gs** out,
-                    hipStream_t s) {
+// one sweep direction's schedule and layouts into a new handle (*out owns it, also on failure)
+static int gs_build(const mlamg_csr* A, bool backward, bool block, const GsKnobs& knobs,
+                    mlamg_gs** out, hipStream_t s) {
+  mlamg_gs* G = *out = new mlamg_gs();
+  G->A = A;
+  G->block = block;
   const int64_t n = A->n_rows;
   // MLAMG_TIMING=1: host phase times of the schedule analysis on stderr
   static const bool timing = std::getenv("MLAMG_TIMING") != nullptr;
@@ -1341,129 +1160,21 @@ static int gs_build(const mlamg_csr* A, bool backward, bool block, mlamg_gs** ou
     MLAMG_HIP(hipMemcpyAsync(ij.data(), A->indices, sizeof(int32_t) * A->nnz, hipMemcpyDeviceToHost, s));
   MLAMG_HIP(hipStreamSynchronize(s));
   phase("copy_in");
-  std::vector<int32_t> level(n, 0), req(n, 0);
-  int32_t nlev = 0;
-  // rows in sweep order; `before(j, i)`: row j is swept before row i
-  auto before = [backward](int64_t j, int64_t i) { return backward ? j > i : j < i; };
-  for (int64_t t = 0; t < n; ++t) {
-    const int64_t i = backward ? n - 1 - t : t;
-    int32_t L = req[i];
-    for (int k = ip[i]; k < ip[i + 1]; ++k) {
-      const int32_t j = ij[k];
-      if (j != i && before(j, i)) L = std::max(L, level[j] + 1);
-    }
-    level[i] = L;
-    for (int k = ip[i]; k < ip[i + 1]; ++k) {
-      const int32_t j = ij[k];
-      if (j != i && before(i, j)) req[j] = std::max(req[j], L + 1);
-    }
-    nlev = std::max(nlev, L + 1);
-  }
-  auto* G = new mlamg_gs();
-  G->A = A;
-  G->block = block;
-  G->backward = backward;
-  G->n_levels = nlev;
-  G->level_ptr.assign(nlev + 1, 0);
-  for (int64_t i = 0; i < n; ++i) G->level_ptr[level[i] + 1]++;
-  for (int32_t l = 0; l < nlev; ++l) G->level_ptr[l + 1] += G->level_ptr[l];
-  std::vector<int32_t> rows(n), fill(G->level_ptr.begin(), G->level_ptr.end() - 1);
-  for (int64_t i = 0; i < n; ++i) rows[fill[level[i]]++] = (int32_t)i;
-  if (hipMalloc(&G->rows, sizeof(int32_t) * std::max<int64_t>(n, 1)) != hipSuccess) {
-    delete G;
-    set_error("gs_create: hipMalloc failed");
-    return MLAMG_ENOMEM;
-  }
-  if (n) (void)hipMemcpy(G->rows, rows.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice);
-  for (int32_t l = 0; l < nlev; ++l)
-    G->max_level_rows = std::max(G->max_level_rows, G->level_ptr[l + 1] - G->level_ptr[l]);
+  GsPlan P;
+  gs_plan_structure(ip.data(), ij.data(), n, backward, P);
   phase("levels");
-  if (hipMalloc(&G->d_level_ptr, sizeof(int32_t) * (nlev + 1)) != hipSuccess) {
-    (void)hipFree(G->rows);
-    delete G;
-    set_error("gs_create: hipMalloc failed");
-    return MLAMG_ENOMEM;
-  }
-  (void)hipMemcpy(G->d_level_ptr, G->level_ptr.data(), sizeof(int32_t) * (nlev + 1),
-                  hipMemcpyHostToDevice);
-  // level-ordered packed copy for k_gs_pipe (rows with <= 8 off-diagonals)
   {
-    int32_t mo = 0;
-    for (int64_t i = 0; i < n; ++i) {
-      int32_t c = 0;
-      for (int k = ip[i]; k < ip[i + 1]; ++k) c += ij[k] != i;
-      mo = std::max(mo, c);
-    }
-    G->max_off = mo;
-    const int K = mo <= 4 ? 4 : (mo <= 8 ? 8 : 0);
-    int32_t ml = 0;
-    for (int64_t i = 0; i < n; ++i) ml = std::max(ml, ip[i + 1] - ip[i]);
-    G->max_len = ml;
-    // the copies below serve one-workgroup sweeps only: levels wider than they take are swept
-    // one launch per level straight from the CSR arrays, so such schedules skip them (C4-size
-    // operators: ~1 GB of host packing and upload per sweep direction)
-    if (!K && ml <= 8 * kGsWaveMaxLPR && G->max_level_rows <= kGsBlockMaxLevelRows) {
-      std::vector<int32_t> wp((size_t)n * 4);
-      for (int64_t p = 0; p < n; ++p) {
-        const int32_t i = rows[p];
-        wp[4 * p] = i;
-        wp[4 * p + 1] = ip[i];
-        wp[4 * p + 2] = ip[i + 1] - ip[i];
-        wp[4 * p + 3] = 0;
-      }
-      if (hipMalloc(&G->wpos, sizeof(int32_t) * std::max<size_t>(wp.size(), 4)) == hipSuccess) {
-        if (n) (void)hipMemcpy(G->wpos, wp.data(), sizeof(int32_t) * wp.size(), hipMemcpyHostToDevice);
-      } else {
-        G->wpos = nullptr;  // optional: the plain one-workgroup kernel takes these rows
-      }
-      setup_wring(G, ip, ij, level, rows);
-    }
-    if (K && G->max_level_rows <= 2 * kGsBlock) {
-      std::vector<double> ax(A->nnz);
+    std::vector<double> ax;
+    if (P.packed) {  // only the packed copy holds values: other schedules leave A's on the device
+      ax.resize(A->nnz);
       if (A->nnz)
         MLAMG_HIP(hipMemcpy(ax.data(), A->data, sizeof(double) * A->nnz, hipMemcpyDeviceToHost));
-      std::vector<int32_t> pcol((size_t)n * K, -1);
-      std::vector<double> pval((size_t)n * K, 0.0), pdiag(n, 0.0);
-      for (int64_t p = 0; p < n; ++p) {
-        const int32_t i = rows[p];
-        int c = 0;
-        for (int k = ip[i]; k < ip[i + 1]; ++k) {
-          if (ij[k] == i) {
-            pdiag[p] = ax[k];  // the last stored diagonal entry counts, as in the sweep
-          } else {
-            pcol[(size_t)p * K + c] = ij[k];
-            pval[(size_t)p * K + c] = ax[k];
-            ++c;
-          }
-        }
-        if (block) pdiag[p] = pdiag[p] != 0.0 ? 1.0 / pdiag[p] : 0.0;  // Dinv = pinv(A_ii)
-      }
-      phase("pack");
-      const size_t m = std::max<size_t>((size_t)n * K, 1), nn = std::max<int64_t>(n, 1);
-      if (hipMalloc(&G->pk_col, sizeof(int32_t) * m) == hipSuccess &&
-          hipMalloc(&G->pk_val, sizeof(double) * m) == hipSuccess &&
-          hipMalloc(&G->pk_diag, sizeof(double) * nn) == hipSuccess &&
-          hipMalloc(&G->b_lvl, sizeof(double) * nn) == hipSuccess) {
-        if (n) {
-          (void)hipMemcpy(G->pk_col, pcol.data(), sizeof(int32_t) * n * K, hipMemcpyHostToDevice);
-          (void)hipMemcpy(G->pk_val, pval.data(), sizeof(double) * n * K, hipMemcpyHostToDevice);
-          (void)hipMemcpy(G->pk_diag, pdiag.data(), sizeof(double) * n, hipMemcpyHostToDevice);
-        }
-        G->pk_k = K;
-        phase("pack_upload");
-        static const char* prefer_ring = std::getenv("MLAMG_GS_PREFER_RING");  // A/B knob
-        if (!(prefer_ring && prefer_ring[0] == '1')) setup_window(G, ip, ij, level, rows, pcol, K);
-        phase("window");
-        if (K == kGsRingK && G->win_rw == 0) setup_ring(G, level, rows, pcol);
-      } else {  // optional: the sweep falls back to the plain kernels
-        for (void* q : {(void*)G->pk_col, (void*)G->pk_val, (void*)G->pk_diag, (void*)G->b_lvl})
-          if (q) (void)hipFree(q);
-        G->pk_col = nullptr;
-        G->pk_val = G->pk_diag = G->b_lvl = nullptr;
-      }
     }
+    gs_plan_layouts(ip.data(), ij.data(), ax.data(), block, knobs, P);
   }
-  *out = G;
+  phase("layouts");
+  MLAMG_TRY(gs_upload(G, P));
+  phase("upload");
   return MLAMG_OK;
 }
 
@@ -1475,14 +1186,13 @@ int mlamg_gs_create_ex(const mlamg_csr* A, int sweep, int block, mlamg_gs** out,
   MLAMG_REQUIRE(sweep >= 0 && sweep <= 2, "sweep must be 0 forward, 1 backward, 2 symmetric");
   MLAMG_REQUIRE(block == 0 || block == 1, "block must be 0 or 1");
   hipStream_t s = S(stream);
-  mlamg_gs* G = nullptr;
-  MLAMG_TRY(gs_build(A, sweep == 1, block == 1, &G, s));
-  if (sweep == 2) {
-    int rc = gs_build(A, true, block == 1, &G->bwd, s);
-    if (rc != MLAMG_OK) {
-      mlamg_gs_destroy(G);
-      return rc;
-    }
+  const GsKnobs knobs = GsKnobs::from_env();
+  mlamg_gs* G = nullptr;  // a failed build leaves its half-built handle here, or in G->bwd
+  int rc = gs_build(A, sweep == 1, block == 1, knobs, &G, s);
+  if (rc == MLAMG_OK && sweep == 2) rc = gs_build(A, true, block == 1, knobs, &G->bwd, s);
+  if (rc != MLAMG_OK) {
+    mlamg_gs_destroy(G);
+    return rc;
   }
   *out = G;
   return MLAMG_OK;
@@ -1495,12 +1205,7 @@ int mlamg_gs_create(const mlamg_csr* A, mlamg_gs** out, void* stream) {
 int mlamg_gs_destroy(mlamg_gs* G) {
   if (G) {
     if (G->bwd) mlamg_gs_destroy(G->bwd);
-    for (void* q : {(void*)G->rows, (void*)G->d_level_ptr, (void*)G->pk_col, (void*)G->pk_val,
-                    (void*)G->pk_diag, (void*)G->b_lvl, (void*)G->wcol, (void*)G->d_clev,
-                    (void*)G->win_xl, (void*)G->wpos, (void*)G->rcol, (void*)G->rpv,
-                    (void*)G->rcode, (void*)G->rxl, (void*)G->wr_code, (void*)G->wr_pv,
-                    (void*)G->wr_len, (void*)G->wr_d, (void*)G->wr_st})
-      if (q) (void)hipFree(q);
+    gs_release(G, 0);
     delete G;
   }
   return MLAMG_OK;
@@ -1509,6 +1214,15 @@ int mlamg_gs_destroy(mlamg_gs* G) {
 int mlamg_gs_levels(const mlamg_gs* G, int32_t* n_levels) {
   MLAMG_REQUIRE(G && n_levels, "NULL argument");
   *n_levels = G->n_levels;
+  return MLAMG_OK;
+}
+
+int mlamg_gs_path(const mlamg_gs* G, int which, int32_t* path) {
+  MLAMG_REQUIRE(G, "G is NULL");
+  MLAMG_REQUIRE(path, "path is NULL");
+  MLAMG_REQUIRE(which == 0 || which == 1, "which must be 0 (own schedule) or 1 (backward half)");
+  MLAMG_REQUIRE(which == 0 || G->bwd, "which = 1 needs a symmetric handle");
+  *path = which ? G->bwd->path : G->path;
   return MLAMG_OK;
 }
 

@@ -124,6 +124,26 @@ class GaussSeidel:
         call("mlamg_gs_mv_path", self.handle, int(k), ctypes.byref(p))
         return int(p.value)
 
+    PATHS = ("LEVELS", "WORKGROUP", "WAVE", "WRING", "PIPE", "PIPE_LDS", "RING", "WINDOW")
+
+    def _path(self, which):
+        p = ctypes.c_int32()
+        call("mlamg_gs_path", self.handle, which, ctypes.byref(p))
+        return int(p.value)
+
+    @property
+    def path(self):
+        """The kernel a single-vector sweep runs on this handle's own schedule (mlamg_gs_path):
+        an index into PATHS."""
+        return self._path(0)
+
+    @property
+    def path_backward(self):
+        """The same for the backward half of a symmetric sweep."""
+        if self.sweep_dir != "symmetric":
+            raise ValueError("path_backward needs sweep='symmetric'")
+        return self._path(1)
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h:

@@ -12,7 +12,8 @@ LIB = os.path.join(ROOT, "ml-amg_amd", "mlamg", "libmlamg_hip.so")
 
 pytestmark = pytest.mark.skipif(not os.path.exists(LIB), reason="libmlamg_hip.so not built")
 
-NAMES = ("mlamg_gs_sweep_mv", "mlamg_gs_mv_path", "mlamg_hier_set_mv_gauss_seidel")
+NAMES = ("mlamg_gs_sweep_mv", "mlamg_gs_mv_path", "mlamg_gs_path",
+         "mlamg_hier_set_mv_gauss_seidel")
 
 
 def test_symbols_are_exported_and_bound():
@@ -48,6 +49,10 @@ def test_arguments_are_checked_without_gpu():
     refused(lib.mlamg_gs_mv_path(G, 4, None), b"path is NULL")
     refused(lib.mlamg_gs_mv_path(G, 0, ctypes.byref(path)), b"k must be in [1, MLAMG_MV_MAX")
     refused(lib.mlamg_gs_mv_path(G, 65, ctypes.byref(path)), b"k must be in [1, MLAMG_MV_MAX")
+    refused(lib.mlamg_gs_path(None, 0, ctypes.byref(path)), b"G is NULL")
+    refused(lib.mlamg_gs_path(G, 0, None), b"path is NULL")
+    refused(lib.mlamg_gs_path(G, -1, ctypes.byref(path)), b"which must be 0")
+    refused(lib.mlamg_gs_path(G, 2, ctypes.byref(path)), b"which must be 0")
     assert path.value == -7
     refused(lib.mlamg_hier_set_mv_gauss_seidel(None, 1), b"H is NULL")
     with pytest.raises(_lib.MlamgError, match="G is NULL"):

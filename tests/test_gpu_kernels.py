@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import gs_cases
 from conftest import golden_csr
 
 pytestmark = pytest.mark.gpu
@@ -470,15 +471,18 @@ def _P1(golden):
                                   "grid_256", "nine_point_48", "grid_160", "grid_400",
                                   "nine_point_300"))
 def test_gauss_seidel_both_schedules(ml, oracle, torch_cuda, case):
-    """Level-scheduled GS through every schedule: the pipelined one-workgroup kernel (levels of
-    <= 1024 rows: grid_200; <= 2048: grid_1100 diagonals; cube_24 planes), the plain
-    one-workgroup kernel (rows with more than 8 off-diagonals), the per-level launches (a level
-    wider than 8192 rows), the windowed sweep (levels of <= 512 rows with <= 8 off-diagonals on
-    1-4 sweeping waves: grid_60, cube_12, nine_point_48 whose couplings span 2 levels and the
-    unsorted / zero-diagonal case on one, nine_point_300 on 3 with 8 slots per row, grid_160
-    on 3, grid_200 and grid_256 on 4, grid_400 on 4 with 2 rows per lane) — bitwise the sequential pyamg
-    sweep, including rows stored in non-ascending order, a zero diagonal (row left unchanged)
-    and a duplicated diagonal entry; three sweeps per launch."""
+    """Level-scheduled GS through four of its eight paths, each asserted (gs.path against
+    gs_cases.BOTH_SCHEDULES, the table the host planner's test checks on the CPU): the per-level
+    launches (LEVELS: wide_levels, a level wider than 8192 rows), the pipelined one-workgroup
+    kernel with two rows per thread (PIPE: grid_1100, anti-diagonal levels of up to 1100 rows),
+    the long-row ring sweep (WRING: long_rows, 25 entries a row) and the windowed sweep (WINDOW,
+    levels of <= 512 rows with <= 8 off-diagonals on 1-4 sweeping waves: grid_60, cube_12,
+    nine_point_48 whose couplings span 2 levels and the unsorted / zero-diagonal case on one,
+    nine_point_300 on 3 with 8 slots per row, grid_160 on 3, grid_200, grid_256 and cube_24 on
+    4, grid_400 on 4 with 2 rows per lane; the "_lds" cases are small enough for k_gs_lds but
+    take the window, which comes first). The other four paths: test_gauss_seidel_every_path.
+    Bitwise the sequential pyamg sweep, including rows stored in non-ascending order, a zero
+    diagonal (row left unchanged) and a duplicated diagonal entry; three sweeps per launch."""
     rs = np.random.RandomState(11)
     if case == "wide_levels":
         n = 30000  # diagonal + a sparse upper band: a few levels of ~10^4 independent rows
@@ -529,6 +533,7 @@ def test_gauss_seidel_both_schedules(ml, oracle, torch_cuda, case):
     x0 = rs.randn(A.shape[0])
     # stored rows as they are (duplicates included: pyamg takes the last diagonal entry)
     gs = ml.multigrid.GaussSeidel(ml.sparse.DeviceCSR.from_scipy(A, check=False))
+    assert gs.PATHS[gs.path] == gs_cases.PATH_NAMES[gs_cases.BOTH_SCHEDULES[case][1]], case
     ref = oracle.gauss_seidel(A, x0.copy(), b, iterations=3)
     xd = torch_cuda.as_tensor(x0.copy()).cuda()
     gs.sweep(xd, torch_cuda.as_tensor(b).cuda(), 3)
@@ -536,6 +541,41 @@ def test_gauss_seidel_both_schedules(ml, oracle, torch_cuda, case):
     assert np.array_equal(got, ref), (case, gs.n_levels)
     if case != "unsorted_zero_diag":  # the reference-facing entry point
         assert np.array_equal(ml.multigrid.gauss_seidel(A, b, x0.copy(), nu=3), ref)
+
+
+@pytest.mark.parametrize("case", sorted(gs_cases.EVERY_PATH))
+def test_gauss_seidel_every_path(ml, oracle, torch_cuda, monkeypatch, case):
+    """The paths test_gauss_seidel_both_schedules does not reach (RING, PIPE_LDS with 4 and 8
+    slots, PIPE with one row per thread and 4 and 8 slots, PIPE with two on the 9,000-row slab,
+    WAVE and WORKGROUP with and without a knob), each also on the unsorted / zero-diagonal /
+    duplicate-diagonal matrix where it takes packed rows: the path asserted (both halves of a
+    symmetric handle), then three sweeps bitwise the sequential one, in both arithmetics and
+    all three directions. Knobs (MLAMG_GS_NO_*) are read when the handle is created."""
+    build, knobs, path = gs_cases.EVERY_PATH[case]
+    for k in knobs:
+        monkeypatch.setenv("MLAMG_GS_" + k, "1")
+    A = build()
+    rs = np.random.RandomState(12)
+    b, x0 = rs.randn(A.shape[0]), rs.randn(A.shape[0])
+    Ad = ml.sparse.DeviceCSR.from_scipy(A, check=False)
+    bd = torch_cuda.as_tensor(b).cuda()
+    for block in (False, True):
+        for sweep in ("forward", "backward", "symmetric"):
+            gs = ml.multigrid.GaussSeidel(Ad, sweep, block=block)
+            assert gs.PATHS[gs.path] == gs_cases.PATH_NAMES[path], (case, sweep, block)
+            if sweep == "symmetric":
+                assert gs.PATHS[gs.path_backward] == gs_cases.PATH_NAMES[path], (case, block)
+            xd = torch_cuda.as_tensor(x0.copy()).cuda()
+            gs.sweep(xd, bd, 3)
+            ref = x0.copy()
+            if block:
+                oracle.pyamg_block_gauss_seidel(A, ref, b, 3, sweep)
+            elif sweep == "forward":
+                oracle.gauss_seidel(A, ref, b, 3)
+            else:
+                oracle.pyamg_gauss_seidel(A, ref, b, 3, sweep)
+            got = xd.cpu().numpy()
+            assert np.array_equal(got.view(np.int64), ref.view(np.int64)), (case, sweep, block)
 
 
 def test_amg_2_v_gauss_seidel(golden, ml):
