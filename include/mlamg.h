@@ -217,7 +217,12 @@ int mlamg_csr_scale_rows(const mlamg_csr* A, const double* d, int reverse, mlamg
                          void* stream);
 
 /* lambda_max of Dinv@A (ARPACK eigs k=1 'LM' in multigrid.py:105) by Lanczos on the similar
- * symmetric D^-1/2 A D^-1/2 (A symmetric with positive diagonal). *lam_host written; syncs. */
+ * symmetric D^-1/2 A D^-1/2 (A symmetric with positive diagonal). *lam_host written; syncs.
+ * At most max_iter steps, which may be more than n (no reorthogonalisation: in finite precision
+ * the tridiagonal can need more than n rows); scratch for 2 max_iter doubles is allocated. The
+ * stop test |theta - theta_prev| <= tol |theta| between checks 32 steps apart is a stagnation
+ * test, not an error bound. A row without a stored diagonal entry, or with a zero, negative or
+ * non-finite one, gives MLAMG_EINVAL and leaves *lam_host and *iters_host untouched. */
 int mlamg_lambda_max_dinvA(const mlamg_csr* A, int max_iter, double tol, uint64_t seed,
                            double* lam_host, int* iters_host, void* stream);
 

@@ -13,6 +13,7 @@
 // the result is deterministic.
 #include "common.hpp"
 #include "reduce.hpp"
+#include "tridiag.hpp"
 
 #include <cmath>
 
@@ -77,20 +78,34 @@ __device__ __forceinline__ uint64_t splitmix(uint64_t x) {
   return x ^ (x >> 31);
 }
 
-// d_i = a_ii (sum of the stored diagonal entries), dinv = 1/d; q = random; partial = sum d q^2
+// What k_lz_init found on the diagonal that the D inner product cannot take (bits of *bad).
+enum : unsigned { kDiagMissing = 1u, kDiagZero = 2u, kDiagNegative = 4u, kDiagNonFinite = 8u };
+
+// d_i = a_ii (sum of the stored diagonal entries), dinv = 1/d; q = random; partial = sum d q^2;
+// *bad |= the kinds of unusable diagonal entries met (an atomic only from a thread that met one)
 __global__ __launch_bounds__(256) void k_lz_init(const int32_t* __restrict__ indptr,
                                                  const int32_t* __restrict__ indices,
                                                  const double* __restrict__ vals, int64_t n,
                                                  uint64_t seed, double* __restrict__ d,
                                                  double* __restrict__ dinv,
                                                  double* __restrict__ q,
-                                                 double* __restrict__ partial) {
+                                                 double* __restrict__ partial,
+                                                 unsigned* __restrict__ bad) {
   __shared__ double red[4];
   double acc = 0.0;
+  unsigned kinds = 0;
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     double di = 0.0;
+    bool stored = false;
     for (int k = indptr[i]; k < indptr[i + 1]; ++k)
-      if (indices[k] == (int32_t)i) di += vals[k];
+      if (indices[k] == (int32_t)i) {
+        di += vals[k];
+        stored = true;
+      }
+    if (!stored) kinds |= kDiagMissing;
+    else if (di == 0.0) kinds |= kDiagZero;
+    else if (di < 0.0) kinds |= kDiagNegative;
+    else if (!(di <= 1.7976931348623157e308)) kinds |= kDiagNonFinite;  // NaN or inf
     d[i] = di;
     dinv[i] = 1.0 / di;
     const uint64_t r = splitmix(seed * 0x100000001B3ull + (uint64_t)i);
@@ -101,35 +116,7 @@ __global__ __launch_bounds__(256) void k_lz_init(const int32_t* __restrict__ ind
   const double t = block_sum_all<256>(acc, red);
   __syncthreads();
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
-}
-
-// number of eigenvalues of the symmetric tridiagonal (a[0..m), b[1..m)) smaller than x
-static int sturm_count(const std::vector<double>& a, const std::vector<double>& b, int m, double x) {
-  int cnt = 0;
-  double q = 1.0;
-  for (int i = 0; i < m; ++i) {
-    const double bb = i > 0 ? b[i] * b[i] : 0.0;
-    q = (a[i] - x) - (i > 0 ? bb / q : 0.0);
-    if (q == 0.0) q = -1e-300;
-    if (q < 0.0) ++cnt;
-  }
-  return cnt;
-}
-
-static double tridiag_max_eig(const std::vector<double>& a, const std::vector<double>& b, int m) {
-  double lo = a[0], hi = a[0];
-  for (int i = 0; i < m; ++i) {
-    const double r = (i > 0 ? std::fabs(b[i]) : 0.0) + (i + 1 < m ? std::fabs(b[i + 1]) : 0.0);
-    lo = std::min(lo, a[i] - r);
-    hi = std::max(hi, a[i] + r);
-  }
-  for (int it = 0; it < 200; ++it) {
-    const double mid = 0.5 * (lo + hi);
-    if (mid <= lo || mid >= hi) break;
-    if (sturm_count(a, b, m, mid) == m) hi = mid;  // all eigenvalues < mid
-    else lo = mid;
-  }
-  return hi;
+  if (kinds) atomicOr(bad, kinds);
 }
 
 int launch_spmv_plain(const mlamg_csr* A, const double* x, double* y, hipStream_t s);
@@ -151,9 +138,13 @@ extern "C" int mlamg_lambda_max_dinvA(const mlamg_csr* A, int max_iter, double t
     return MLAMG_OK;
   }
   const int nbv = (int)std::min<int64_t>(1024, (n + 255) / 256);
-  const int m_max = (int)std::min<int64_t>(max_iter, n);
+  // No cap at n: without reorthogonalisation the Lanczos vectors lose orthogonality in finite
+  // precision, and T_j may have to grow past n steps (with ghost copies of converged Ritz
+  // values, which do not move its largest eigenvalue) before that eigenvalue settles.
+  const int m_max = max_iter;
+  const int64_t slots = (int64_t)m_max + 2;  // of alpha and of beta
   double* base = nullptr;
-  MLAMG_HIP(hipMalloc(&base, sizeof(double) * (n * 6 + nbv + 2 * (m_max + 2) + 1)));
+  MLAMG_HIP(hipMalloc(&base, sizeof(double) * (n * 6 + nbv + 2 * slots + 2)));
   struct Free {
     double* p;
     ~Free() { (void)hipFree(p); }
@@ -164,19 +155,22 @@ extern "C" int mlamg_lambda_max_dinvA(const mlamg_csr* A, int max_iter, double t
   double* Q[3] = {dinv + n, dinv + 2 * n, dinv + 3 * n};  // q_prev, q, w
   double* partial = dinv + 4 * n;
   double* alpha = partial + nbv;
-  double* beta = alpha + (m_max + 2);
-  double* nrm0 = beta + (m_max + 2);
+  double* beta = alpha + slots;
+  double* nrm0 = beta + slots;
+  unsigned* bad = reinterpret_cast<unsigned*>(nrm0 + 1);
   MLAMG_HIP(hipMemsetAsync(Q[0], 0, sizeof(double) * n, s));
-  MLAMG_HIP(hipMemsetAsync(beta, 0, sizeof(double) * (m_max + 2), s));
+  MLAMG_HIP(hipMemsetAsync(beta, 0, sizeof(double) * slots, s));
+  MLAMG_HIP(hipMemsetAsync(bad, 0, sizeof(unsigned), s));
   hipLaunchKernelGGL(k_lz_init, dim3(nbv), dim3(256), 0, s, A->indptr, A->indices, A->data, n,
-                     seed, d, dinv, Q[1], partial);
+                     seed, d, dinv, Q[1], partial, bad);
   hipLaunchKernelGGL(k_reduce_to, dim3(1), dim3(1024), 0, s, partial, nbv, nrm0, 1);
   hipLaunchKernelGGL(k_lz_scale, dim3(nbv), dim3(256), 0, s, Q[1], nrm0, n);
   MLAMG_HIP(hipGetLastError());
 
   const int kCheck = 32;
-  std::vector<double> ha(m_max + 2), hb(m_max + 2);
+  std::vector<double> ha(slots), hb(slots);
   double theta_prev = -1.0, theta = 0.0;
+  unsigned hbad = 0;
   int j = 0;
   bool done = false;
   while (!done) {
@@ -198,7 +192,16 @@ extern "C" int mlamg_lambda_max_dinvA(const mlamg_csr* A, int max_iter, double t
     MLAMG_HIP(hipGetLastError());
     MLAMG_HIP(hipMemcpyAsync(ha.data(), alpha, sizeof(double) * j, hipMemcpyDeviceToHost, s));
     MLAMG_HIP(hipMemcpyAsync(hb.data(), beta, sizeof(double) * (j + 1), hipMemcpyDeviceToHost, s));
+    if (j <= kCheck)  // the first read also brings what k_lz_init saw on the diagonal
+      MLAMG_HIP(hipMemcpyAsync(&hbad, bad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     MLAMG_HIP(hipStreamSynchronize(s));
+    // 1/d and the D-norm need a positive diagonal; with any other the recurrence runs on inf
+    // and NaN, which the breakdown test below would take for convergence
+    MLAMG_REQUIRE(!(hbad & kDiagMissing), "a row has no stored diagonal entry");
+    MLAMG_REQUIRE(!(hbad & kDiagZero), "a row has a zero diagonal entry");
+    MLAMG_REQUIRE(!(hbad & kDiagNegative),
+                  "a row has a negative diagonal entry (positive diagonal required)");
+    MLAMG_REQUIRE(!(hbad & kDiagNonFinite), "a row has a non-finite diagonal entry");
     // T_j: diagonal ha[0..j), off-diagonal hb[1..j)
     int m = j;
     bool breakdown = false;
@@ -214,6 +217,7 @@ extern "C" int mlamg_lambda_max_dinvA(const mlamg_csr* A, int max_iter, double t
     if (theta_prev > 0.0 && std::fabs(theta - theta_prev) <= tol * std::fabs(theta)) done = true;
     theta_prev = theta;
   }
+  MLAMG_REQUIRE(std::isfinite(theta), "non-finite result (non-finite matrix entries?)");
   *lam_host = theta;
   if (iters_host) *iters_host = j;
   return MLAMG_OK;

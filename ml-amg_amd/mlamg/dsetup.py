@@ -462,7 +462,7 @@ def lambda_max_distributed(Ag, hx, lo, hi, comm, max_iter=20000, tol=1e-15, seed
     z = torch.zeros(n, dtype=torch.float64, device=dev)
     nrm0 = math.sqrt(_allsum(comm, float(torch.sum(d_own * (q[lo:hi] * q[lo:hi])))))
     q[lo:hi] *= (1.0 / nrm0) if nrm0 > 0.0 else 0.0
-    m_max = min(int(max_iter), n)
+    m_max = int(max_iter)  # not capped at n: csrc/eig.hip
     ha, hb = [], [0.0]
     theta_prev, theta = -1.0, 0.0
     j = 0

@@ -166,7 +166,16 @@ def gauss_seidel(A, b, x, L=None, U=None, nu=2):
 
 
 def lambda_max_dinv_a(A, max_iter=20000, tol=1e-15, seed=0):
-    """Largest eigenvalue of Dinv@A (ARPACK eigs k=1 'LM' at ns/lib/multigrid.py:105)."""
+    """Largest eigenvalue of Dinv@A (ARPACK eigs k=1 'LM' at ns/lib/multigrid.py:105) by the
+    device Lanczos of csrc/eig.hip, with the number of steps taken: (lambda, iters). A must be
+    symmetric with a positive diagonal; any other diagonal raises.
+
+    The run stops when the largest Ritz value moves by no more than tol (relative) between two
+    checks 32 steps apart, or at a breakdown, or after max_iter steps (which may exceed n). That
+    is a stagnation test and no error bound: a Ritz value never exceeds lambda_max beyond
+    rounding, so a loose tol can only return too small a value, by an amount that tol does not
+    bound. At the default tol the result is held to 1e-12 of the exact value
+    (tests/test_gpu_lambda_max.py)."""
     A_dev = as_device(A)
     lam = ctypes.c_double()
     its = ctypes.c_int()

@@ -176,11 +176,37 @@ def test_executor_from_setup_bitwise(prob, world, min_rows):
         np.testing.assert_allclose(h, h_ref, rtol=1e-12, atol=0)
 
 
+def _lanczos_on_ranks(A, world):
+    """dsetup.lambda_max_distributed alone on A's row slabs -> [(lambda, iters)] by rank."""
+    import torch
+    from mlamg import dsetup, partition
+    n = A.shape[0]
+    ranges = partition.row_ranges(n, world)
+
+    def fn(comm):
+        lo, hi = ranges[comm.rank]
+        A_own = dsetup.split_rows(A, world, comm.rank)
+        Ag = dsetup._gs_csr(torch.arange(lo, hi, device="cuda"), A_own, n, n)
+        hx = dsetup.GHalo(comm, dsetup._ghosts(A_own, lo, hi), ranges)
+        return dsetup.lambda_max_distributed(Ag, hx, lo, hi, comm)
+
+    return dsetup.run_threads(world, fn)
+
+
 @pytest.mark.parametrize("world", [1, 3])
 def test_distributed_lanczos_and_cycle(prob, world):
     import torch
+    import lanczos_model as lm
+    from mlamg import multigrid
     A, H = prob
     n = A.shape[0]
+    # the n = 150 jump matrix, which needs more than n steps (worlds 1 and 2)
+    J, ref = lm.matrix("jump1d_150"), lm.reference("jump1d_150")
+    lam_1, its_1 = multigrid.lambda_max_dinv_a(J)
+    got = _lanczos_on_ranks(J, min(world, 2))
+    assert all(g == got[0] for g in got)
+    assert abs(got[0][0] - lam_1) <= 1e-13 * lam_1 and abs(got[0][0] - ref) <= 1e-12 * ref
+    assert got[0][1] > J.shape[0] and its_1 > J.shape[0], (got[0][1], its_1)
     Ss = _setups(A, world, alpha=0.1, max_coarse=200, min_rows=0)
     for S in Ss:
         assert S.lams == Ss[0].lams  # every rank reduces the same partials in the same order
