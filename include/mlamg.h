@@ -823,6 +823,31 @@ int mlamg_pcg_solve_mv(mlamg_pcg* C, const double* B, int64_t ldb, double* X, in
  * most that call's k); syncs */
 int mlamg_pcg_iters_mv(const mlamg_pcg* C, int32_t* iters, int k, void* stream);
 
+/* mlamg_gmres on the n x k block (B, X) (multivectors as above; B != X): the restarted MGS GMRES
+ * of mlamg_gmres run in lock-step on every column, so that each inner step applies the operator
+ * (one SpMM), the preconditioner (one zero-guess block cycle of M) and every Gram-Schmidt dot and
+ * update once for all k columns. COLUMN j OF X, info[j], inner_iters[j] AND COLUMN j OF THE HISTORY
+ * ARE BITWISE WHAT mlamg_gmres RETURNS ON COLUMN j ALONE with the same rtol, restart, maxiter and
+ * x_is_zero: every dot keeps the single kernels' partition and order per column, and each column
+ * has its own Hessenberg columns, rotations, status, ptol and ||b||. A column whose inner stop
+ * fires is frozen for the rest of that restart cycle; one that has converged, has ||b|| = 0
+ * (x = b, 0 steps, info 0), starts below rtol ||b|| or broke down is frozen for good (its x is no
+ * longer written) while the others continue; the solve ends when no column is left or after
+ * maxiter restart cycles. X (device) holds the initial guesses (x_is_zero: known to be 0) and the
+ * results. info, inner_iters: HOST, k entries. presid_hist_host (HOST, nullable): hist_cap x k
+ * row-major, column j receives the preconditioned residual estimate / ||b_j|| of its first
+ * min(inner_iters[j], hist_cap) steps. M's block cycle takes what mlamg_hier_vcycle_mv takes: a
+ * dense or a PCG coarse solve, Gauss-Seidel levels after mlamg_hier_set_mv_gauss_seidel, VECTOR
+ * operators after mlamg_hier_set_mv_vector (A in the VECTOR format is then summed in the canonical
+ * order, as mlamg_gmres sums it); MLAMG_EUNSUPPORTED otherwise, and for a GMRES coarse solve or a
+ * factored prolongation. The (restart + 1) n x k Krylov blocks live in M's Krylov workspace.
+ * NULL arguments, k out of range, ld < k and B == X return MLAMG_EINVAL before any device call.
+ * Syncs; not capturable. */
+int mlamg_gmres_mv(const mlamg_csr* A, mlamg_hier* M, const double* B, int64_t ldb, double* X,
+                   int64_t ldx, int k, double rtol, int restart, int maxiter, int x_is_zero,
+                   int32_t* info, int32_t* inner_iters, double* presid_hist_host, int hist_cap,
+                   void* stream);
+
 /* Sampled dense-dense product on S's pattern (csrc/sddmm.hip; the gradient of amg_loss with
  * respect to a prolongator's stored values, mlamg/loss.py):
  *   out[e] = alpha * sum_{c<k} U[row(e), c] * V[col(e), c] + beta * out[e]

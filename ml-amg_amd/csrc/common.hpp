@@ -357,10 +357,12 @@ int pcg_solve_mv_impl(mlamg_pcg* C, const double* B, int64_t ldb, double* X, int
 // hier_coarse_cycle on a block (hier_mv.hip): one zero-guess cycle of H with its level 0 as a
 // coarse level on the n x k block B (leading dimension k); *X_out (leading dimension k) lies in
 // H's block workspace. done (nullable): a device flag that turns every launch of the cycle into a
-// no-op once it is raised. MLAMG_EUNSUPPORTED where mlamg_hier_vcycle_mv refuses, and for a
-// coarsest solve that is not dense.
+// no-op once it is raised. MLAMG_EUNSUPPORTED where mlamg_hier_vcycle_mv refuses; and, unless
+// `outer` (the block GMRES's preconditioner: H is the user's hierarchy, not a Krylov solver's
+// inner one), for a coarsest solve that is not dense, a Gauss-Seidel level and a VECTOR operator
+// whatever H's switches say.
 int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
-                         const int32_t* done = nullptr);
+                         const int32_t* done = nullptr, bool outer = false);
 // restarted left-preconditioned GMRES (scipy's algorithm) with one V-cycle of M as
 // preconditioner (gmres.hip); rel_out (optional): final ||b - A x|| / ||b||
 int gmres_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, double* x, double rtol,

@@ -17,23 +17,9 @@
 // rotations and the inner stop test — runs on the device in one thread (k_gm_arnoldi, the same
 // operations as scipy's numpy code), so an inner iteration costs one status read; the
 // triangular solve and the restart logic stay on the host, once per restart cycle.
-#include "common.hpp"
-#include "reduce.hpp"
-
-#include <cmath>
+#include "gmres.hpp"
 
 namespace mlamg {
-
-constexpr int kGmThreads = 256;
-constexpr int kGmMaxBlocks = 1024;
-
-// sum of np partials by a whole workgroup of kGmThreads, every thread gets it; behind a barrier,
-// because red may still be read from the sum before
-__device__ __forceinline__ double gm_total(const double* __restrict__ partial, int np,
-                                           double* red) {
-  __syncthreads();
-  return partials_total_all<kGmThreads>(partial, np, red);
-}
 
 // out[0] = a . b, fixed order: per-workgroup partials, summed in order by the last-arriving
 // workgroup (agent-scope acquire/release on the arrival counter)
@@ -143,33 +129,10 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_update(double* __restrict__ x
   }
 }
 
-// LAPACK dlartg (3.10+, the safe-scaling version scipy's get_lapack_funcs('lartg') binds):
-// c f + s g = r, -s f + c g = 0
-__host__ __device__ static void lartg(double f, double g, double* c, double* s, double* r) {
-  if (g == 0.0) {
-    *c = 1.0;
-    *s = 0.0;
-    *r = f;
-  } else if (f == 0.0) {
-    *c = 0.0;
-    *s = g > 0 ? 1.0 : -1.0;
-    *r = fabs(g);
-  } else {
-    const double d = sqrt(f * f + g * g);
-    *c = fabs(f) / d;
-    *r = f > 0 ? d : -d;
-    *s = g / *r;
-  }
-}
-
-// One Arnoldi step's small-matrix work on the device, by one thread — what the host did with
-// the read-back column, the same operations in the same order (so the same bits): Hessenberg
-// column from the MGS coefficients and norms, exact-solution test, the past rotations, a new
-// rotation (lartg), the rotated right-hand side and the preconditioned residual estimate; then
-// the inner stop (presid <= ptol or breakdown) raises `done`, which the next iteration's kernels
-// and V-cycle (the hierarchy's own flag) read, so the host needs one status read per iteration.
-// st: [0] presid, [1] h1 (the scale of v_{col+1}), [2] breakdown, [3] last column, [4] steps,
-// [5] ||w||^2 before the projections (h0^2).
+// One Arnoldi step's small-matrix work on the device, by one thread (gm_arnoldi_step: what the
+// host did with the read-back column); then the inner stop raises `done`, which the next
+// iteration's kernels and V-cycle (the hierarchy's own flag) read, so the host needs one status
+// read per iteration.
 __global__ __launch_bounds__(kGmThreads) void k_gm_arnoldi(
     int col, int ldh, const double* __restrict__ scal, const double* __restrict__ p_h0,
     const double* __restrict__ p_h1, int np, double* __restrict__ Hd, double* __restrict__ giv,
@@ -182,41 +145,8 @@ __global__ __launch_bounds__(kGmThreads) void k_gm_arnoldi(
   __syncthreads();
   const double w1 = gm_total(p_h1, np, red);
   if (threadIdx.x != 0) return;
-  st[5] = w0;
-  auto H = [&](int c, int k) -> double& { return Hd[(size_t)c * ldh + k]; };
-  const double h0 = sqrt(w0);
-  for (int k = 0; k <= col; ++k) H(col, k) = scal[k];
-  const double h1 = sqrt(w1);
-  H(col, col + 1) = h1;
-  bool breakdown = false;
-  if (h1 <= eps * h0) {  // exact solution indicator
-    H(col, col + 1) = 0.0;
-    breakdown = true;
-  }
-  st[1] = h1;
-  for (int k = 0; k < col; ++k) {  // past rotations
-    const double c = giv[2 * k], sn = giv[2 * k + 1];
-    const double n0 = H(col, k), n1 = H(col, k + 1);
-    H(col, k) = c * n0 + sn * n1;
-    H(col, k + 1) = -sn * n0 + c * n1;
-  }
-  double c, sn, mag;
-  lartg(H(col, col), H(col, col + 1), &c, &sn, &mag);
-  giv[2 * col] = c;
-  giv[2 * col + 1] = sn;
-  H(col, col) = mag;
-  H(col, col + 1) = 0.0;
-  const double t2 = -sn * S[col];
-  S[col] = c * S[col];
-  S[col + 1] = t2;
-  const double presid = fabs(t2);
-  const int steps = (int)st[4];
-  if (hist && steps < hist_cap) hist[steps] = presid / bnrm2;
-  st[0] = presid;
-  st[2] = breakdown ? 1.0 : 0.0;
-  st[3] = (double)col;
-  st[4] = (double)(steps + 1);
-  if (presid <= ptol || breakdown) *done = 1;
+  if (gm_arnoldi_step(col, ldh, scal, w0, w1, Hd, giv, S, st, eps, ptol, bnrm2, hist, hist_cap))
+    *done = 1;
 }
 
 struct GmWork {
@@ -336,7 +266,6 @@ int gmres_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, double* x, do
   double presid = 0.0, rnorm = 0.0;
   std::vector<double> h((size_t)restart * (restart + 1), 0.0), S(restart + 1, 0.0),
       y(restart + 1, 0.0);
-  auto H = [&](int c, int k) -> double& { return h[(size_t)c * (restart + 1) + k]; };
   double* V0 = W.V;
   auto Vk = [&](int k) { return W.V + (int64_t)k * W.ld; };
   for (int iteration = 0; iteration < maxiter; ++iteration) {
@@ -406,16 +335,7 @@ int gmres_impl(const mlamg_csr* A, mlamg_hier* M, const double* b, double* x, do
     breakdown = st_h[2] != 0.0;
     iters = (int)st_h[4];
     if (col == restart) col = restart - 1;
-    if (H(col, col) == 0.0) S[col] = 0.0;
-    for (int k = 0; k <= col; ++k) y[k] = S[k];
-    for (int k = col; k > 0; --k) {
-      if (y[k] != 0.0) {
-        y[k] /= H(k, k);
-        const double t = y[k];
-        for (int j = 0; j < k; ++j) y[j] -= t * H(k, j);
-      }
-    }
-    if (y[0] != 0.0) y[0] /= H(0, 0);
+    gm_small_solve(h.data(), restart + 1, S.data(), col, y.data());
     MLAMG_HIP(hipMemcpyAsync(W.y, y.data(), sizeof(double) * (col + 1), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_gm_update, dim3(nb), dim3(kGmThreads), 0, s, x, W.V, n, W.ld, W.y,
                        col + 1);

@@ -7,7 +7,8 @@
 // asked, mlamg_hier_set_mv_gauss_seidel) smooths its block in place with the block sweep of
 // gs_mv.hip, as the single path does with gs_sweep_impl. The coarsest solve is the dense inverse
 // or the block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner
-// hierarchy. An operator in the VECTOR format (taken once the hierarchy asked,
+// hierarchy; the block GMRES (gmres_mv.hip) preconditions with hier_coarse_cycle_mv on the
+// hierarchy itself, which then takes what mlamg_hier_vcycle_mv takes. An operator in the VECTOR format (taken once the hierarchy asked,
 // mlamg_hier_set_mv_vector) goes through the canonical-order kernel of spmm_vec.hip, every other
 // one through k_spmm_stream: each launch follows its own operator's format, as the single path's.
 // One routine, level_mv, runs every level for both callers.
@@ -192,9 +193,13 @@ static int level_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, int64_t
 
 namespace mlamg {
 int hier_coarse_cycle_mv(mlamg_hier* H, const double* B, double** X_out, int k, hipStream_t s,
-                         const int32_t* done) {
-  MLAMG_TRY(
-      mv_refusals(H, false, false, false, "block cycle of a Krylov solver's inner hierarchy"));
+                         const int32_t* done, bool outer) {
+  if (outer) {
+    MLAMG_TRY(mv_refusals(H, true, H->mv_gs, H->mv_vec, "block cycle of mlamg_gmres_mv"));
+  } else {
+    MLAMG_TRY(
+        mv_refusals(H, false, false, false, "block cycle of a Krylov solver's inner hierarchy"));
+  }
   MLAMG_TRY(hier_prepare(H));
   MvWork W;
   MLAMG_TRY(mv_workspace(H, k, s, done, &W, true));

@@ -187,6 +187,8 @@ SIGNATURES = {
     "mlamg_pcg_iters_mv": (c_int, [c_vp, P_i32, c_int, c_vp]),
     "mlamg_gmres": (c_int, [c_vp, c_vp, c_vp, c_vp, c_dbl, c_int, c_int, c_int, P_int, P_int,
                             c_vp, c_int, c_vp]),
+    "mlamg_gmres_mv": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_int, c_int,
+                               c_int, P_i32, P_i32, c_vp, c_int, c_vp]),
     "mlamg_csr_symmetric": (c_int, [c_vp, c_dbl, P_int, c_vp]),
     "mlamg_hier_set_smoothing": (c_int, [c_vp, c_int, c_int]),
     "mlamg_hier_set_done_check": (c_int, [c_vp, c_int]),

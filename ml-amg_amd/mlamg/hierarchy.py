@@ -1007,7 +1007,11 @@ class Hierarchy:
         ||b - A x|| <= rtol ||b||; the Krylov acceleration of ns/preconditioner/PyAMG.py:119).
         x0=None starts from 0. Returns x (numpy in -> numpy out, tensor in -> tensor out), plus
         {"info", "inner_iters", "presid"} (presid: preconditioned residual estimate / ||b|| per
-        Krylov step) with return_info=True."""
+        Krylov step) with return_info=True. A 2-D b is a block of right-hand sides:
+        gmres_multi(b, x0, ...)."""
+        if getattr(b, "ndim", 1) == 2:
+            return self.gmres_multi(b, x0, rtol=rtol, restart=restart, maxiter=maxiter,
+                                    return_info=return_info)
         A = self.levels[0].A if self.levels else self.Ac
         bd = to_device_vec(b)
         xd = torch.zeros_like(bd) if x0 is None else to_device_vec(x0).clone()
@@ -1025,6 +1029,45 @@ class Hierarchy:
         k = min(inner.value, cap)
         return x, {"info": info.value, "inner_iters": inner.value,
                    "presid": np.array(hist[:k])}
+
+    def gmres_multi(self, B, X0=None, rtol=1e-5, restart=20, maxiter=None, return_info=False):
+        """gmres on the (n, k) block B of k <= 64 right-hand sides at once (mlamg_gmres_mv): the
+        columns run in lock-step, so every Krylov step applies the operator, the preconditioner
+        (one block cycle) and each Gram-Schmidt reduction once for all k columns. Column j of the
+        result, and its entries of the info, are bitwise gmres(B[:, j], X0[:, j], ...): each
+        column stops on its own ||b_j - A x_j|| <= rtol ||b_j|| and is frozen from then on.
+        X0=None starts from 0. B (and X0) may be column slices of wider tensors. Returns X (numpy
+        in -> numpy out, tensor in -> tensor out), plus {"info": (k,), "inner_iters": (k,),
+        "presid": list of k arrays} with return_info=True. The preconditioner is the block
+        cycle, with cycle_multi's coarse solves and refusals: Gauss-Seidel levels need
+        enable_block_gauss_seidel() first, 'vector'-format operators enable_block_vector()."""
+        from .sparse import mv_block
+        A = self.levels[0].A if self.levels else self.Ac
+        n = A.shape[0]
+        as_tensor = isinstance(B, torch.Tensor)
+        Bd = B if as_tensor and B.is_cuda and B.dtype == torch.float64 else to_device_vec(B)
+        k, ldb = mv_block(Bd, n, "B")
+        if X0 is None:
+            Xd = torch.zeros((n, k), dtype=torch.float64, device=Bd.device)
+        else:
+            Xd = to_device_vec(X0).clone()
+            if tuple(Xd.shape) != (n, k):
+                raise ValueError(f"X0 has shape {tuple(Xd.shape)}, expected {(n, k)}")
+        cap = 4096
+        hist = np.zeros((cap, k), dtype=np.float64)
+        info = np.zeros(k, dtype=np.int32)
+        inner = np.zeros(k, dtype=np.int32)
+        P_i32 = ctypes.POINTER(ctypes.c_int32)
+        self._solve_call("mlamg_gmres_mv", A.handle, self.handle, ptr(Bd), ldb, ptr(Xd), k, k,
+                         float(rtol), int(restart), int(maxiter or 0), int(X0 is None),
+                         info.ctypes.data_as(P_i32), inner.ctypes.data_as(P_i32),
+                         hist.ctypes.data, cap, stream_ptr())
+        self.check_coarse()  # a broken-down coarse solve inside the preconditioner
+        X = Xd if as_tensor else Xd.cpu().numpy()
+        if not return_info:
+            return X
+        return X, {"info": info, "inner_iters": inner,
+                   "presid": [hist[: min(int(inner[j]), cap), j].copy() for j in range(k)]}
 
     def gmres_householder(self, b, x0=None, tol=1e-5, maxiter=None, return_info=False):
         """pyamg.krylov.gmres(A, b, x0, tol, maxiter, M=one V-cycle) with its default
