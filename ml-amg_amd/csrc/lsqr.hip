@@ -7,7 +7,9 @@
 // roundings ((1/beta)*u, t - alfa*u, x + t1*w, ...); the scalar recurrences (Givens rotation
 // _sym_ortho, norm / condition estimates, stopping tests istop 1..7 in scipy's order) run in one
 // device thread, so the iteration needs no host round trip. Norms are fixed-order device
-// reductions where scipy calls BLAS ddot: iterates agree to fp64 rounding, not bitwise.
+// reductions where scipy calls BLAS ddot, and squares are products where scipy's v**2 is libm's
+// pow: against scipy the iterates agree to fp64 rounding; against scipy restated with those two
+// substitutions (tests/lsqr_model.py) x, istop and itn are bitwise (tests/test_gpu_lsqr.py).
 //
 // Per iteration, all on one stream, every kernel a no-op once the done flag is up:
 //   t = A v | u = t - alfa u, sum u^2 | beta, anorm | u /= beta | t = A^T u | v = t - beta v,
@@ -299,8 +301,9 @@ int mlamg_lsqr(const mlamg_csr* A, const mlamg_csr* AT, const double* b, double*
     hip(hipStreamSynchronize(s), "sync");
     return r;
   };
-  // x = 0, u = b, beta = bnorm = ||b||
-  hip(hipMemsetAsync(x, 0, sizeof(double) * std::max<int64_t>(n, 1), s), "memset");
+  // x = 0, u = b, beta = bnorm = ||b||. x is the caller's and has exactly n entries (v and w are
+  // ours and have at least one)
+  if (n > 0) hip(hipMemsetAsync(x, 0, sizeof(double) * n, s), "memset");
   hip(hipMemcpyAsync(u, b, sizeof(double) * m, hipMemcpyDeviceToDevice, s), "copy");
   const double bnorm = sqrt(norm_sq(u, m));
   const double beta = bnorm;
