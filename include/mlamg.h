@@ -314,6 +314,57 @@ int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_
                        const int64_t* k_ptr, const int64_t* k_ptr_host, int64_t nb, float* vec,
                        int32_t* idx, void* stream);
 
+/* The wide layers of ns/model/ali_interp.py InterpolationNetwork (ResidualBlock of TAGConv(K=5)
+ * up to 256 channels, EdgeModel 513 -> 256 -> ... -> 1 with LayerNorms), fp32, device pointers
+ * (csrc/gnn_wide.hip). Conventions as above: a size outside the limit stated at a prototype
+ * returns MLAMG_EINVAL and writes nothing; every launch covers its whole index range. */
+/* mlamg_gnn_linear's contract and epilogue on LDS tiles of the f32-input matrix cores
+ * (v_mfma_f32_32x32x2_f32): every output's sum runs k = 0 .. K-1 in one accumulator chain from
+ * +0.0 (no split-K), so Y is value-equal to mlamg_gnn_linear wherever both accept the shape (a
+ * zero-padded k step can turn a -0.0 sum into +0.0). M == 0 returns without a launch.
+ * Limits: 1 <= K <= 1024, 1 <= N <= 256, M >= 0, beta in {0, 1}, rc in {1, N} when R is given. */
+int mlamg_gnn_linear_wide(const float* X, int64_t M, int K, const float* W, const float* b, int N,
+                          int act, float beta, const float* R, int rc, float* Y, void* stream);
+/* mlamg_gnn_propagate on wider rows: column f of Y is bitwise mlamg_gnn_propagate on column f of
+ * X (the same edge-order fmaf chain). n == 0 returns without a launch. Limits: 1 <= F <= 256. */
+int mlamg_gnn_propagate_wide(const int32_t* tptr, const int32_t* teid, const int32_t* src,
+                             const float* w, const float* X, int64_t n, int F, float* Y,
+                             void* stream);
+/* torch LayerNorm over each row of X[rows][F] (biased variance, eps; weight and bias nullable:
+ * 1 and 0), then + R[rows][F] (nullable), then act (0 none, 1 relu): EdgeModel.forward's order.
+ * A wave per row; mean and variance are summed in double (lane l takes f = l, l + 64, ... in that
+ * order, then the wave butterfly of csrc/reduce.hpp). rows == 0 returns without a launch.
+ * Limits: 1 <= F <= 256, rows >= 0. */
+int mlamg_gnn_layer_norm(const float* X, int64_t rows, int F, const float* weight,
+                         const float* bias, float eps, const float* R, int act, float* Y,
+                         void* stream);
+/* The first EdgeModel block without the E x (2F + 1) concatenation: with U = X W[:, :F]^T and
+ * V = X W[:, F:2F]^T (n x H each, two mlamg_gnn_linear_wide calls), per edge e
+ *   h = ((U[src_e] + V[tgt_e]) + ea_e * w) + b,  out[e] = relu(LayerNorm(h) * g + beta)
+ * (w[H] = W[:, 2F], LayerNorm as mlamg_gnn_layer_norm). E == 0 returns without a launch.
+ * Limits: 1 <= H <= 256, E >= 0. */
+int mlamg_gnn_edge_in(const int32_t* src, const int32_t* tgt, const float* U, const float* V,
+                      const float* ea, int64_t E, int H, const float* w, const float* b,
+                      const float* g, const float* beta, float eps, float* out, void* stream);
+/* out[e] = |(v[e] - mean) / std| over the E values of v, std unbiased (torch.std's default,
+ * ali_interp.py:174); mean and the squared deviations are summed in double in the fixed order
+ * of csrc/reduce.hpp on a grid that depends on E alone. Limits: 2 <= E. */
+int mlamg_gnn_standardize_abs(const float* v, int64_t E, float* out, void* stream);
+
+/* greedy_coarsening (ns/lib/greedy.py:13-36) on HOST CSR arrays (csrc/greedy.cpp; touches no
+ * device): rows whose dominance |a_ii| / sum_j |a_ij| reaches theta go to F in index order; then,
+ * while undecided rows remain, the one of smallest dominance (ties: smallest index) goes to C
+ * and each of its still undecided neighbours, in ascending index, has its dominance recomputed
+ * over its undecided and F columns as they stand and moves to F at once if it reaches theta.
+ * F[n], C[n] (capacity n each) receive the rows in the reference's append order, *nF and *nC
+ * their counts. Sums are fp64 in ascending column order. EINVAL, before anything is written, on
+ * a NULL argument, n < 0, rows that are not canonical (ascending, duplicate-free, in range), a
+ * missing or zero diagonal, a non-finite value, or a NaN theta. Stored zeros off the diagonal are
+ * no neighbours (scipy's nonzero() drops them). */
+int mlamg_greedy_coarsening(int64_t n, const int32_t* indptr, const int32_t* indices,
+                            const double* data, double theta, int32_t* F, int32_t* C,
+                            int64_t* nF, int64_t* nC);
+
 /* Seeded Bellman-Ford exactly as the reference's modified_bellman_ford (ns/lib/graph.py:7-53;
  * replaces that call at utils/evaluate_model.py:57, utils/evaluate_dataset.py:87): sweeps over
  * the edges (i -> j, weight g_ij rounded to fp32 like the torch COO values, ns/lib/sparse.py:28)

@@ -11,6 +11,8 @@ Mirrors the reference modules on the hot path:
                                                   strength of connection on the device)
   mlamg.preconditioner  <- ns/preconditioner     (MLAMG PC: initialize/update/apply)
   mlamg.gnn             <- ns/model/agg_interp.py (FullAggNet inference: AggNet, MPNN)
+  mlamg.interp          <- ns/model/ali_interp.py (InterpolationNetwork inference: the learned P)
+  mlamg.greedy          <- ns/lib/greedy.py      (greedy C/F splitting, on the host)
   mlamg.fitness         <- utils/train_dataset.py:81-138 (the GA's conv-factor fitness, batched)
   mlamg.loss            <- ns/model/loss.py      (amg_loss on a block of test vectors, fp64, and
                                                   its gradient with respect to P's values)
@@ -26,7 +28,8 @@ import importlib
 __version__ = "0.1.0"
 
 _SUBMODULES = ("multigrid", "graph", "sparse", "strength", "gnn", "hierarchy",
-               "preconditioner", "problems", "gridio", "distributed", "loss", "fitness", "_lib")
+               "preconditioner", "problems", "gridio", "distributed", "loss", "fitness", "_lib",
+               "interp", "greedy")
 
 
 def __getattr__(name):

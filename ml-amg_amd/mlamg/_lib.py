@@ -132,6 +132,17 @@ SIGNATURES = {
     "mlamg_gnn_instance_norm_seg": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_float, c_vp,
                                             c_vp]),
     "mlamg_gnn_topk_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    # the wide layers of InterpolationNetwork (csrc/gnn_wide.hip) and its host C/F splitting
+    "mlamg_gnn_linear_wide": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_int,
+                                      ctypes.c_float, c_vp, c_int, c_vp, c_vp]),
+    "mlamg_gnn_propagate_wide": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp,
+                                         c_vp]),
+    "mlamg_gnn_layer_norm": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, ctypes.c_float, c_vp, c_int,
+                                     c_vp, c_vp]),
+    "mlamg_gnn_edge_in": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp,
+                                  c_vp, ctypes.c_float, c_vp, c_vp]),
+    "mlamg_gnn_standardize_abs": (c_int, [c_vp, c_i64, c_vp, c_vp]),
+    "mlamg_greedy_coarsening": (c_int, [c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp, c_vp]),
     "mlamg_bellman_ford_pyamg_seg_plan_create": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vpp, c_vp]),
     "mlamg_bellman_ford_pyamg_seg_plan_destroy": (c_int, [c_vp]),
     "mlamg_bellman_ford_pyamg_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp,

@@ -7,11 +7,16 @@ Reference surface (ns/preconditioner/MLAMG.py):
   'mlamg_jacobi_weight' (2/3, :66); apply runs amg_2_v (:148-197) from x0 = np.random.normal
   (:209) with the weighted-Jacobi smoother until ||b - A x||_2 <= amg_rtol, at most 500 cycles.
 
-What differs: the reference builds P with a learned GNN (InterpolationNetwork + greedy C/F
-splitting, :105-120), which needs torch_geometric and trained weights that are not shipped. Here P
-is the smoothed-aggregation prolongator of seeded Bellman-Ford aggregates, built on the GPU
-(option 'mlamg_alpha', default 0.1), or any P handed in via `MLAMG.set_prolongator`. The cycle,
-stopping rule and I/O contract are the reference's. The PC works with petsc4py when present and
+What differs: the reference always builds P with a learned GNN (greedy C/F splitting, then
+InterpolationNetwork, :105-120) and fails without its trained weights, which are not shipped. Here
+that setup runs when the option 'mlamg_pnet_model' names a saved state_dict (with
+'mlamg_greedy_theta', default 0.56, :65-67): mlamg.greedy.greedy_coarsening on the host,
+mlamg.interp.InterpolationNetwork.forward_mat on the device (torch_geometric's layers restated,
+parity with it unpinned: see mlamg/interp.py), then the Galerkin product and the coarse
+factorisation of Hierarchy.two_level. Without the option P is the smoothed-aggregation
+prolongator of seeded Bellman-Ford aggregates, built on the GPU (option 'mlamg_alpha', default
+0.1), or any P handed in via `MLAMG.set_prolongator`. The cycle, stopping rule and I/O contract
+are the reference's. The PC works with petsc4py when present and
 with any duck-typed object offering getOperators()/getOptionsPrefix() otherwise (no PETSc here).
 """
 from __future__ import annotations
@@ -94,6 +99,8 @@ class MLAMG:
         self.jacobi_weight = opts.getScalar(f"{prefix}jacobi_weight", 2.0 / 3.0)
         self.alpha = opts.getScalar(f"{prefix}alpha", 0.1)
         self.max_iter = opts.getInt(f"{prefix}max_iter", 500)
+        self.coarsening_theta = opts.getScalar(f"{prefix}greedy_theta", 0.56)
+        self.pnet_model_fname = opts.getString(f"{prefix}pnet_model", "")
         self.update(pc)
 
     def set_prolongator(self, P):
@@ -112,11 +119,30 @@ class MLAMG:
         self.A = A
         if self._P_user is not None:
             P = self._P_user
+        elif getattr(self, "pnet_model_fname", ""):
+            P = self._learned_P(A)
         else:
             H = Hierarchy.build(A, alpha=self.alpha, max_levels=2, max_coarse=0,
                                 jacobi_weight=self.jacobi_weight, finalize=False)
             P = H.levels[0].P
         self.H = Hierarchy.two_level(A, P, omega=self.jacobi_weight)
+
+    def _learned_P(self, A):
+        """The reference's setup (MLAMG.py:105-120): load the P-net, greedy C/F splitting,
+        forward_mat."""
+        from .greedy import greedy_coarsening
+        from .interp import InterpolationNetwork
+        self.P_net = InterpolationNetwork()
+        try:
+            state_dict = torch.load(self.pnet_model_fname, weights_only=True)
+            self.P_net.model.load_state_dict(state_dict)
+            self.P_net.eval()
+        except Exception as e:
+            raise RuntimeError(f'Could not load PNet model "{self.pnet_model_fname}": {e}')
+        self.P_net.to(torch.device("cuda", torch.cuda.current_device()))
+        _, F, C = greedy_coarsening(A, self.coarsening_theta)
+        self.P_amg = self.P_net.forward_mat(A, C, F)
+        return self.P_amg
 
     def apply(self, pc, X, Y):
         try:
