@@ -44,6 +44,7 @@ typedef struct mlamg_dense mlamg_dense;
 typedef struct mlamg_blockdense mlamg_blockdense;
 typedef struct mlamg_hier mlamg_hier;
 typedef struct mlamg_gs mlamg_gs;
+typedef struct mlamg_poly mlamg_poly;
 typedef struct mlamg_pcg mlamg_pcg;
 typedef struct mlamg_comm mlamg_comm;
 
@@ -539,6 +540,38 @@ int mlamg_gs_mv_path(const mlamg_gs* G, int k, int32_t* path);
  * NULL arguments and which outside 0..1 return MLAMG_EINVAL before G is read. */
 int mlamg_gs_path(const mlamg_gs* G, int which, int32_t* path);
 
+/* ---------------------------------------------------------------- polynomial smoother
+ * pyamg relaxation.polynomial(A, x, b, coefficients, iterations) (pyamg absent: parity unpinned,
+ * the arithmetic is restated in DESIGN.md §32), the sweep behind presmoother=('chebyshev', ...).
+ * coeffs_host (HOST, n_coeffs >= 1 finite numbers) in pyamg's order, coeffs[0] on the highest
+ * power: what smoothing.setup_chebyshev keeps, -chebyshev_polynomial_coefficients(...)[:-1].
+ * A (square) must outlive the handle; the handle owns three device vectors of A's size (r and two
+ * h). A non-square A, n_coeffs < 1 and a non-finite coefficient return MLAMG_EINVAL before any
+ * device call. */
+int mlamg_poly_create(const mlamg_csr* A, const double* coeffs_host, int n_coeffs,
+                      mlamg_poly** out, void* stream);
+int mlamg_poly_destroy(mlamg_poly* S);
+/* rows of the operator and the number of coefficients (each nullable) */
+int mlamg_poly_info(const mlamg_poly* S, int64_t* rows, int* n_coeffs);
+/* `iterations` times, in place on x (DEVICE): r = b - A x; h = c[0] r; h = c[i] r + A h for
+ * i = 1 .. m-1; x = x + h, every multiply and add rounded on its own and A h the row sum of A's
+ * active storage format (mlamg_spmv's): bitwise relaxation.polynomial in the formats that sum in
+ * scipy's order. Costs m SpMV launches and m passes over A per iteration and nothing else: r and
+ * c[0] r leave the first launch together, the last one adds into x (m = 1: one launch and a
+ * copy). b NULL: a zero right-hand side. x_is_zero != 0: x is not read and counts as all +0.0 (the
+ * same bits as the general path on such an x; for finite A), which turns the first pass over A
+ * into one elementwise launch. No host synchronisation; b != x. */
+int mlamg_poly_sweep(const mlamg_poly* S, double* x, const double* b, int iterations,
+                     int x_is_zero, void* stream);
+/* The same sweep on a block of k right-hand sides (multivectors as in the multi-vector section
+ * below: row-major n x k, ld >= k, 1 <= k <= MLAMG_MV_MAX), X in place, the matrix stream read
+ * once for all k columns per pass. COLUMN j OF X IS BITWISE mlamg_poly_sweep ON COLUMN j: in
+ * scipy's order, or in the canonical CSR-vector order while A is in the VECTOR format. The k-wide
+ * work space belongs to the handle and grows on demand, never inside a stream capture
+ * (MLAMG_EINVAL there: sweep once at that width before capturing). B may be NULL; B != X. */
+int mlamg_poly_sweep_mv(const mlamg_poly* S, double* X, int64_t ldx, const double* B, int64_t ldb,
+                        int k, int iterations, int x_is_zero, void* stream);
+
 /* ---------------------------------------------------------------- coarse direct solve
  * Replaces spla.factorized/splu (multigrid.py:168; MLAMG.py:122): the coarse operator is
  * inverted densely on the device (Gauss-Jordan, partial pivoting, fp64) once; each solve is a
@@ -602,6 +635,14 @@ int mlamg_hier_set_factored_prolong(mlamg_hier* H, int level, const mlamg_csr* A
  * sweep, in place; ns/lib/multigrid.py:175,184 — the reference amg_2_v), or NULL for weighted
  * Jacobi (default) */
 int mlamg_hier_set_level_smoother(mlamg_hier* H, int level, const mlamg_gs* gs);
+/* smoother of one level: a polynomial handle built on that level's operator (pyamg's
+ * presmoother = postsmoother = ('chebyshev', {'iterations': iterations})), or NULL for the
+ * default. Each of the cycle's nu_pre / nu_post sweeps is then `iterations` (>= 1) iterations of
+ * mlamg_poly_sweep, n_coeffs passes over A each; coarse levels pre-smooth from a known-zero
+ * guess, and a residual the cycle already holds is not recomputed. A level has one smoother:
+ * setting this clears a Gauss-Seidel handle and mlamg_hier_set_level_smoother clears this one.
+ * Both the single and the block cycle take such levels (bitwise per column). */
+int mlamg_hier_set_level_polynomial(mlamg_hier* H, int level, const mlamg_poly* S, int iterations);
 /* Coarsest solve without a size cap (replaces spla.factorized / splu, ns/lib/multigrid.py:168,
  * MLAMG.py:122, where a dense inverse no longer fits): PCG on A (SPD) preconditioned by one
  * V-cycle of the inner hierarchy M (built on A, finalised), to ||b - A x|| <= rtol ||b||, at most

@@ -314,6 +314,21 @@ int spmv_fadd(const mlamg_csr* A, const int32_t* agg, const double* e, double* y
               const double* dinv_w, const int32_t* done, hipStream_t s);
 int spmv_set(const mlamg_csr* A, const double* x, double* y, const int32_t* done, hipStream_t s,
              double* smooth_x = nullptr, const double* smooth_dinv = nullptr);
+// the polynomial smoother's SpMV launches (spmv.hip) and its sweeps (poly.hip; arguments already
+// validated). r_ready: r holds b - A x on entry, and the first iteration does not recompute it
+int poly_first(const mlamg_csr* A, const double* b, const double* x, double* r, double alpha,
+               const double* xin, double* h, const int32_t* done, hipStream_t s);
+int poly_step(const mlamg_csr* A, double alpha, const double* r, const double* h, bool acc,
+              const double* xin, double* y, const int32_t* done, hipStream_t s);
+int poly_sweep_impl(const mlamg_poly* S, double* x, const double* b, int iterations, bool x_is_zero,
+                    const double* r_ready, const int32_t* done, hipStream_t s);
+int poly_sweep_mv_impl(const mlamg_poly* S, double* X, int64_t ldx, const double* B, int64_t ldb,
+                       int k, int iterations, bool x_is_zero, const double* R_ready, int64_t ldr,
+                       const int32_t* done, hipStream_t s, bool canon);
+// grow S's block work space to k columns (not inside a stream capture)
+int poly_reserve_mv(const mlamg_poly* S, int k);
+int64_t poly_rows(const mlamg_poly* S);
+int poly_terms(const mlamg_poly* S);
 int jacobi_from_residual(double* x, const double* dinv, const double* r, int64_t n,
                          const int32_t* done, hipStream_t s);
 int jacobi_from_zero(double* x, const double* dinv, const double* b, int64_t n,
@@ -398,6 +413,13 @@ int residual_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* 
 int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int64_t ldb,
                     const double* Xin, int64_t ldxin, double* Xout, int64_t ldxout, int k,
                     hipStream_t s, const int32_t* done = nullptr, bool canon = false);
+int poly_first_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                  double* R, int64_t ldr, double alpha, const double* Xin, int64_t ldxin, double* H,
+                  int64_t ldh, int k, hipStream_t s, const int32_t* done = nullptr,
+                  bool canon = false);
+int poly_step_mv(const mlamg_csr* A, double alpha, const double* R, int64_t ldr, const double* H,
+                 int64_t ldh, bool acc, const double* Xin, int64_t ldxin, double* Y, int64_t ldy,
+                 int k, hipStream_t s, const int32_t* done = nullptr, bool canon = false);
 // mode 0: X += d .* R (jacobi_from_residual), mode 1: X = d .* R (jacobi_from_zero)
 int diag_mv(double* X, int64_t ldx, const double* d, const double* R, int64_t ldr, int64_t n,
             int k, int mode, hipStream_t s, const int32_t* done = nullptr);

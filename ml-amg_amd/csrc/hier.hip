@@ -117,10 +117,15 @@ int mlamg::hier_prepare(mlamg_hier* H) {
   return MLAMG_OK;
 }
 
-// smoothing sweeps starting from `cur` (x or tmp); returns buffer holding the result
+// smoothing sweeps starting from `cur` (x or tmp); returns buffer holding the result. A
+// polynomial level alone uses the last two: cur counts as all zero and is not read (zero), or
+// b - A cur is already in r_ready and the first iteration does not recompute it
 static int smooth(const Level& L, const double* b, double*& cur, double* other, int nu,
-                  const int32_t* done, hipStream_t s) {
+                  const int32_t* done, hipStream_t s, bool zero = false,
+                  const double* r_ready = nullptr) {
   if (L.gs) return gs_sweep_impl(L.gs, cur, b, nu, done, s);  // in place, cur unchanged
+  if (L.poly)  // in place as well
+    return poly_sweep_impl(L.poly, cur, b, nu * L.poly_iters, zero, r_ready, done, s);
   for (int i = 0; i < nu; ++i) {
     MLAMG_TRY(jacobi_sweep(L.A, L.dinv, b, cur, other, false, done, s));
     std::swap(cur, other);
@@ -140,7 +145,7 @@ static int correct_and_postsmooth(mlamg_hier* H, size_t l, const double* b, doub
   const int32_t* done = H->cur_done;
   Level& L = H->lv[l];
   const bool last = l + 1 == H->lv.size();
-  const bool fuse_next = !last && H->nu_pre > 0 && !H->lv[l + 1].gs;
+  const bool fuse_next = !last && H->nu_pre > 0 && !H->lv[l + 1].gs && !H->lv[l + 1].poly;
   double* bn = last ? H->bc : H->lv[l + 1].b;
   if (fuse_next) {
     MLAMG_TRY(spmv_set(L.R, L.r, bn, done, s, H->lv[l + 1].x, H->lv[l + 1].dinv));
@@ -169,7 +174,11 @@ static int cycle_coarse(mlamg_hier* H, size_t l, const double* b, double** res, 
   Level& L = H->lv[l];
   double* cur = L.x;
   double* other = L.tmp;
-  if (H->nu_pre > 0 && L.gs) {
+  if (H->nu_pre > 0 && L.poly) {  // from a known-zero guess: cur is written, never read
+    MLAMG_TRY(smooth(L, b, cur, other, H->nu_pre, done, s, true));
+    MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, const_cast<int32_t*>(done),
+                            kNoTol, nullptr, nullptr, nullptr, s));
+  } else if (H->nu_pre > 0 && L.gs) {
     MLAMG_HIP(hipMemsetAsync(cur, 0, sizeof(double) * L.n, s));
     MLAMG_TRY(smooth(L, b, cur, other, H->nu_pre, done, s));
     MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, const_cast<int32_t*>(done),
@@ -195,7 +204,7 @@ static int cycle_coarse(mlamg_hier* H, size_t l, const double* b, double** res, 
 // still in tmp even when the tolerance flag stopped later cycles). Saves one pass over x, d, r.
 static bool fused_presmooth(const mlamg_hier* H) {
   return !H->lv.empty() && H->nu_pre >= 1 && ((H->nu_pre - 1 + H->nu_post) & 1) &&
-         !H->lv[0].gs && H->norm_mode == 0;
+         !H->lv[0].gs && !H->lv[0].poly && H->norm_mode == 0;
 }
 
 // one finest-level cycle; requires L0.r == b - A x on entry, leaves it so on exit (fused mode:
@@ -212,7 +221,11 @@ static int cycle_top(mlamg_hier* H, const double* b, double* x, double* hist, do
   const bool fused = fused_presmooth(H);
   double* cur = x;
   double* other = L.tmp;
-  if (H->nu_pre > 0 && L.gs) {
+  if (H->nu_pre > 0 && L.poly) {  // L.r == b - A x on entry: the first iteration starts from it
+    MLAMG_TRY(smooth(L, b, cur, other, H->nu_pre, done, s, false, L.r));
+    MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, done, kNoTol, nullptr,
+                            nullptr, nullptr, s));
+  } else if (H->nu_pre > 0 && L.gs) {
     MLAMG_TRY(smooth(L, b, cur, other, H->nu_pre, done, s));
     MLAMG_TRY(residual_impl(L.A, b, cur, L.r, nullptr, nullptr, nullptr, done, kNoTol, nullptr,
                             nullptr, nullptr, s));
@@ -379,6 +392,20 @@ int mlamg_hier_set_level_smoother(mlamg_hier* H, int level, const mlamg_gs* gs) 
   MLAMG_REQUIRE(H && level >= 0 && (size_t)level < H->lv.size(), "invalid level");
   MLAMG_REQUIRE(!gs || gs_rows(gs) == H->lv[level].n, "Gauss-Seidel handle of another size");
   H->lv[level].gs = gs;
+  H->lv[level].poly = nullptr;  // one smoother per level
+  H->invalidate_graphs();
+  return MLAMG_OK;
+}
+
+int mlamg_hier_set_level_polynomial(mlamg_hier* H, int level, const mlamg_poly* S,
+                                    int iterations) {
+  MLAMG_REQUIRE(H && level >= 0 && (size_t)level < H->lv.size(), "invalid level");
+  MLAMG_REQUIRE(!S || poly_rows(S) == H->lv[level].n, "polynomial handle of another size");
+  MLAMG_REQUIRE(!S || iterations >= 1, "iterations < 1");
+  Level& L = H->lv[level];
+  L.poly = S;
+  L.poly_iters = S ? iterations : 1;
+  if (S) L.gs = nullptr;  // one smoother per level
   H->invalidate_graphs();
   return MLAMG_OK;
 }
@@ -438,7 +465,8 @@ int mlamg_hier_vcycle(mlamg_hier* H, const double* b, double* x, int n_cycles, d
   hipStream_t s = S(stream);
   // b NULL: a zero right-hand side (the reference's convergence-factor problems, b = 0). The
   // fine-level kernels then take b = +0.0 without reading a vector of zeros (the same bits:
-  // 0.0 - A x); the paths that read b as a vector get a zero buffer
+  // 0.0 - A x; a polynomial level's launches take b = NULL the same way); the paths that read b
+  // as a vector get a zero buffer
   H->zero_rhs = !b;
   if (!b && (H->lv.empty() || H->lv[0].gs)) {
     const int64_t n0 = hier_fine_rows(H);
@@ -526,6 +554,24 @@ static int cycle_bytes(const mlamg_hier* H, bool stored, double* bytes) {
     const double jac = a + bb + dv;
     const double res = a + bb;
     const bool fused = l == 0 && fused_presmooth(H);
+    if (L.poly) {
+      // An iteration is m launches of A: the first also reads b and writes h next to r, every
+      // later one reads r, the last one x too. One coefficient: a launch (reads x as a vector
+      // too) and a copy. The first pre-smoothing iteration starts from the residual the cycle
+      // holds (top) or from a zero guess (below): its first pass is elementwise (16n), and below
+      // its last launch does not read x.
+      const double m = (double)poly_terms(L.poly);
+      const double gen = m > 1 ? (a + bb + 8.0 * n) + (m - 2) * (a + 8.0 * n) + (a + 16.0 * n)
+                               : a + bb + 24.0 * n;
+      const double start = m > 1 ? 16.0 * n + (m - 2) * (a + 8.0 * n) + (a + 8.0 * n) +
+                                       (l == 0 ? 8.0 * n : 0.0)
+                                 : (l == 0 ? 24.0 * n : 16.0 * n);
+      if (H->nu_pre > 0) t += start + (H->nu_pre * L.poly_iters - 1) * gen + res;
+      t += r + p + 8.0 * n;
+      t += H->nu_post * L.poly_iters * gen;
+      if (l == 0) t += res;  // end-of-cycle residual norm; the iterate never leaves x
+      continue;
+    }
     if (H->nu_pre > 0) {
       // first sweep: elementwise at the top (unless fused into the cycle end); below, fused
       // into the restriction kernel above (+ read dinv, write x)

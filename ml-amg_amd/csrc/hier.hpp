@@ -15,6 +15,10 @@ struct Level {
   double* r = nullptr;    // residual
   double* tmp = nullptr;  // ping-pong partner of x
   const mlamg_gs* gs = nullptr;  // Gauss-Seidel smoother (in place) instead of weighted Jacobi
+  // polynomial smoother (in place; poly.hip) instead: poly_iters iterations per sweep. A level has
+  // at most one of gs / poly
+  const mlamg_poly* poly = nullptr;
+  int poly_iters = 1;
   // factored prolongation (opt-in, mlamg_hier_set_factored_prolong): x += t - (w D^-1) A t with
   // t = Agg e, through fac_A (this level's A in the uniform row-pair format), instead of x += P e
   const mlamg_csr* fac_A = nullptr;

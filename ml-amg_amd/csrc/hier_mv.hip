@@ -5,7 +5,9 @@
 // column j keeps the bits of the single-vector cycle on column j. Work buffers are k-wide copies
 // of the level vectors with leading dimension k. A Gauss-Seidel level (taken once the hierarchy
 // asked, mlamg_hier_set_mv_gauss_seidel) smooths its block in place with the block sweep of
-// gs_mv.hip, as the single path does with gs_sweep_impl. The coarsest solve is the dense inverse
+// gs_mv.hip, as the single path does with gs_sweep_impl; a polynomial level (taken without a
+// switch: poly.hip's block sweep is bitwise per column) with poly_sweep_mv_impl, from a zero guess
+// or from the residual block it already holds exactly where the single path does. The coarsest solve is the dense inverse
 // or the block PCG (pcg.hip), whose preconditioner is hier_coarse_cycle_mv on the inner
 // hierarchy; the block GMRES (gmres_mv.hip) preconditions with hier_coarse_cycle_mv on the
 // hierarchy itself, which then takes what mlamg_hier_vcycle_mv takes. An operator in the VECTOR format (taken once the hierarchy asked,
@@ -132,8 +134,11 @@ static int mv_workspace(mlamg_hier* H, int k, hipStream_t s, const int32_t* done
 // two change roles, so `other` stays the one of the pair that `cur` is not; Gauss-Seidel sweeps
 // in place.
 static int smooth(const MvWork& W, const Level& L, const double* B, int64_t ldb, Blk& cur,
-                  Blk& other, int nu) {
+                  Blk& other, int nu, bool zero = false, const double* r_ready = nullptr) {
   if (L.gs) return gs_sweep_mv_impl(L.gs, cur.p, cur.ld, B, ldb, W.k, nu, W.done, W.s);
+  if (L.poly)  // in place; zero: cur is not read; r_ready (ld = k): B - A cur, not recomputed
+    return poly_sweep_mv_impl(L.poly, cur.p, cur.ld, B, ldb, W.k, nu * L.poly_iters, zero,
+                              r_ready, W.k, W.done, W.s, canon(L.A));
   for (int i = 0; i < nu; ++i) {
     MLAMG_TRY(W.jacobi(L, B, ldb, cur, other));
     std::swap(cur, other);
@@ -163,8 +168,14 @@ static int level_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, int64_t
   const int nu = H->nu_pre;
   // the first Jacobi sweep is elementwise: x = Dinv_w B from a zero guess, x += Dinv_w r from an
   // iterate (same roundings as a sweep). Gauss-Seidel has no such shortcut and reads no residual
-  const bool gs_pre = L.gs && nu > 0, jacobi_pre = !L.gs && nu > 0;
-  if (start == ZERO_GUESS) {
+  const bool gs_pre = L.gs && nu > 0, jacobi_pre = !L.gs && !L.poly && nu > 0;
+  if (L.poly && nu > 0) {
+    // the single path's steps (cycle_coarse / cycle_top): a zero guess is not read, a residual the
+    // cycle holds (ITERATE_R) starts the first iteration
+    MLAMG_TRY(smooth(W, L, B, ldb, cur, other, nu, start == ZERO_GUESS,
+                     start == ITERATE_R ? M.r : nullptr));
+    MLAMG_TRY(W.residual(L.A, B, ldb, cur, M.r));
+  } else if (start == ZERO_GUESS) {
     if (jacobi_pre) {
       MLAMG_TRY(diag_mv(cur.p, cur.ld, L.dinv, B, ldb, L.n, k, 1, s, W.done));
     } else {
@@ -176,7 +187,7 @@ static int level_mv(mlamg_hier* H, MvWork& W, size_t l, const double* B, int64_t
     if (start != ITERATE_R && !gs_pre) MLAMG_TRY(W.residual(L.A, B, ldb, cur, M.r));
     if (jacobi_pre) MLAMG_TRY(diag_mv(cur.p, cur.ld, L.dinv, M.r, k, L.n, k, 0, s, W.done));
   }
-  if (nu > 0) {
+  if (nu > 0 && !L.poly) {
     MLAMG_TRY(smooth(W, L, B, ldb, cur, other, gs_pre ? nu : nu - 1));
     MLAMG_TRY(W.residual(L.A, B, ldb, cur, M.r));
   }

@@ -199,6 +199,42 @@ int jacobi_sweep_mv(const mlamg_csr* A, const double* dinv, const double* B, int
   return launch_spmm(A, Xin, ldxin, k, ep, s, canon);
 }
 
+// the polynomial smoother's launches on a block (spmv.hip poly_first / poly_step per column)
+int poly_first_mv(const mlamg_csr* A, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                  double* R, int64_t ldr, double alpha, const double* Xin, int64_t ldxin, double* H,
+                  int64_t ldh, int k, hipStream_t s, const int32_t* done, bool canon) {
+  EpiMV ep{};
+  ep.done = done;
+  ep.op = MV_POLY;
+  ep.alpha = alpha;
+  ep.B = B;
+  ep.ldb = ldb;
+  ep.Xin = Xin;
+  ep.ldxin = ldxin;
+  ep.Y = R;
+  ep.ldy = ldr;
+  ep.H = H;
+  ep.ldh = ldh;
+  return launch_spmm(A, X, ldx, k, ep, s, canon);
+}
+
+int poly_step_mv(const mlamg_csr* A, double alpha, const double* R, int64_t ldr, const double* H,
+                 int64_t ldh, bool acc, const double* Xin, int64_t ldxin, double* Y, int64_t ldy,
+                 int k, hipStream_t s, const int32_t* done, bool canon) {
+  EpiMV ep{};
+  ep.done = done;
+  ep.op = MV_POLY;
+  ep.alpha = alpha;
+  ep.beta = acc ? 1.0 : 0.0;
+  ep.B = R;
+  ep.ldb = ldr;
+  ep.Xin = acc ? Xin : nullptr;
+  ep.ldxin = ldxin;
+  ep.Y = Y;
+  ep.ldy = ldy;
+  return launch_spmm(A, H, ldh, k, ep, s, canon);
+}
+
 // ---------------------------------------------------------------- row-wise vector kernels
 // X[i, :] += d[i] * R[i, :] (mode 0: k_axpy_diag per column) or X[i, :] = d[i] * B[i, :] (mode 1:
 // k_mul_diag per column); one element per thread, columns fastest

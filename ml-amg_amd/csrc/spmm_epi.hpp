@@ -8,7 +8,7 @@
 
 namespace mlamg {
 
-enum MvOp : int { MV_AXPBY = 0, MV_RESID = 1, MV_JACOBI = 2, MV_ADD = 3 };
+enum MvOp : int { MV_AXPBY = 0, MV_RESID = 1, MV_JACOBI = 2, MV_ADD = 3, MV_POLY = 4 };
 
 struct EpiMV {
   int op;
@@ -21,6 +21,11 @@ struct EpiMV {
   double* Y;            // output (AXPBY with beta != 0 and ADD also read it)
   int64_t ldy;
   const int32_t* done;  // nullable stop flag: raised, the launch does nothing
+  // POLY (spmv.hip EPI_POLY per column): Y = alpha B + A X, with Xin set (or beta != 0 for an
+  // all-zero Xin that is not read) Y = Xin + (alpha B + A X); with H set the sweep's first launch
+  // Y = R = B - A X (Y nullable), H = alpha R, with Xin set H = Xin + alpha R (H is not X)
+  double* H;
+  int64_t ldh;
 };
 
 // two adjacent columns at p (the second only when `two`)
@@ -84,6 +89,22 @@ __device__ __forceinline__ void epi_mv(int64_t row, int c, bool two, double s0, 
     const double r0 = b0 - s0, r1 = b1 - s1;
     o0 = x0 + d * r0;
     o1 = x1 + d * r1;
+  } else if (e.op == MV_POLY) {
+    double b0 = 0.0, b1 = 0.0, x0 = 0.0, x1 = 0.0;
+    if (e.B) ld2<VEC>(e.B + row * e.ldb + c, two, b0, b1);
+    if (e.Xin) ld2<VEC>(e.Xin + row * e.ldxin + c, two, x0, x1);
+    if (e.H) {
+      const double r0 = b0 - s0, r1 = b1 - s1;
+      if (e.Y) st2<VEC>(y, two, r0, r1);
+      const double h0 = e.alpha * r0, h1 = e.alpha * r1;
+      st2<VEC>(e.H + row * e.ldh + c, two, e.Xin ? x0 + h0 : h0, e.Xin ? x1 + h1 : h1);
+      return;
+    }
+    const double t0 = e.alpha * b0, t1 = e.alpha * b1;
+    const double h0 = t0 + s0, h1 = t1 + s1;
+    const bool acc = e.Xin || e.beta != 0.0;
+    o0 = acc ? x0 + h0 : h0;
+    o1 = acc ? x1 + h1 : h1;
   } else {  // MV_ADD
     double y0, y1;
     ld2<VEC>(y, two, y0, y1);
@@ -99,7 +120,9 @@ static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 static inline bool mv_vec16(const double* X, int64_t ldx, const EpiMV& ep) {
   bool vec = al16(X) && !(ldx & 1) && al16(ep.Y) && !(ep.ldy & 1);
   if (ep.B) vec = vec && al16(ep.B) && !(ep.ldb & 1);
-  if (ep.op == MV_JACOBI) vec = vec && al16(ep.Xin) && !(ep.ldxin & 1);
+  if (ep.op == MV_JACOBI || (ep.op == MV_POLY && ep.Xin))
+    vec = vec && al16(ep.Xin) && !(ep.ldxin & 1);
+  if (ep.op == MV_POLY && ep.H) vec = vec && al16(ep.H) && !(ep.ldh & 1);
   return vec;
 }
 

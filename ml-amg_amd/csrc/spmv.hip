@@ -13,6 +13,8 @@
 //   JACOBI  y = x + dinv_w*(b - A@x)                               MLAMG.py:145
 //   JACEXP  y = x + (dinv_w*b - M@x), M = (w*Dinv)@A explicit      multigrid.py:44
 //   ADD     y = y + A@x                                            multigrid.py:181 (x += P@e)
+//   POLY    y = alpha*b + A@x (+ xin): one Horner step of pyamg's relaxation.polynomial, or
+//           its first launch r = b - A@x with copy_to = alpha*r (+ xin)      DESIGN.md §32
 // Roofline: HBM-bound. Algorithmic bytes per call = 12*nnz + 4*(n+1) + 8*n_cols + 8*n (+8n per
 // extra vector the epilogue reads/writes), SURVEY.md §8(d).
 // The storage formats these kernels read are built in formats.hip; formats.hpp is the seam.
@@ -24,7 +26,7 @@
 namespace mlamg {
 
 enum EpiOp : int { EPI_AXPBY = 0, EPI_RESID = 1, EPI_JACOBI = 2, EPI_JACEXP = 3, EPI_ADD = 4,
-                   EPI_FADD = 5 };
+                   EPI_FADD = 5, EPI_POLY = 6 };
 
 struct Epi {
   double alpha, beta;
@@ -40,6 +42,11 @@ struct Epi {
   // FADD (factored SA prolongation, k_rowpat_uni only): the kernel's x operand is the virtual
   // vector t = Agg e (t_i = e[agg[i]], 0 where agg[i] < 0) and y += t - dinv * (A t)
   const int32_t* agg;
+  // POLY (polynomial smoother, poly.hip). A Horner step: y = alpha * b + A x, with xin set
+  // y = xin + (alpha * b + A x) (the sweep's last step; beta != 0 stands for an all-zero xin that
+  // is not read). With copy_to set it is the sweep's first launch instead: y = r = b - A x (y
+  // nullable) and copy_to = alpha * r, with xin set copy_to = xin + alpha * r (a one-coefficient
+  // sweep; copy_to must not be the operand x). b NULL: a zero vector, as in RESID.
 };
 
 // A level operator (square) of at most kCachedNnz entries (~100 MB in CSR) is read with ordinary
@@ -78,6 +85,9 @@ __device__ __forceinline__ EpiIn epi_load(int row, const Epi& e) {
   } else if constexpr (OP == EPI_FADD) {
     v.a = e.y[row];
     v.c = e.dinv[row];
+  } else if constexpr (OP == EPI_POLY) {
+    v.a = e.b ? e.b[row] : 0.0;
+    if (e.xin) v.b = e.xin[row];  // else +0.0
   } else {  // EPI_ADD
     v.a = e.y[row];
   }
@@ -114,6 +124,18 @@ __device__ __forceinline__ double epi_store(int row, double s, const EpiIn& v, c
     return 0.0;
   } else if constexpr (OP == EPI_FADD) {
     e.y[row] = v.a + (v.b - v.c * s);
+    return 0.0;
+  } else if constexpr (OP == EPI_POLY) {
+    if (e.copy_to) {  // first launch of a sweep: r and h_0 = c_0 r (one coefficient: x + c_0 r)
+      const double r = v.a - s;
+      if (e.y) e.y[row] = r;
+      const double h = e.alpha * r;
+      e.copy_to[row] = e.xin ? v.b + h : h;
+    } else {  // h = c_i r + A h, the last one added to x (each operation rounds on its own)
+      const double t = e.alpha * v.a;
+      const double h = t + s;
+      e.y[row] = (e.xin || e.beta != 0.0) ? v.b + h : h;
+    }
     return 0.0;
   } else {  // EPI_ADD
     e.y[row] = v.a + s;
@@ -447,6 +469,9 @@ __device__ __forceinline__ void epi_load2(int r, bool both, const Epi& e, EpiIn&
   } else if constexpr (OP == EPI_FADD) {
     ld2(e.y, r, both, u.a, w.a);
     if (!no_dinv) ld2(e.dinv, r, both, u.c, w.c);  // t (u.b, w.b) comes from the x window
+  } else if constexpr (OP == EPI_POLY) {
+    if (e.b) ld2(e.b, r, both, u.a, w.a);
+    if (e.xin) ld2(e.xin, r, both, u.b, w.b);
   } else {  // EPI_ADD
     ld2(e.y, r, both, u.a, w.a);
   }
@@ -475,6 +500,16 @@ __device__ __forceinline__ double epi_value(double s, const EpiIn& v, const Epi&
     return v.b + (t1 - s);
   } else if constexpr (OP == EPI_FADD) {
     return v.a + (v.b - v.c * s);  // x + (t - (w / a_ii) (A t)): x + P e, P = (I - w D^-1 A) Agg
+  } else if constexpr (OP == EPI_POLY) {
+    if (e.copy_to) {
+      const double r = v.a - s;
+      const double h = e.alpha * r;
+      c = e.xin ? v.b + h : h;
+      return r;
+    }
+    const double t = e.alpha * v.a;
+    const double h = t + s;
+    return (e.xin || e.beta != 0.0) ? v.b + h : h;
   } else {  // EPI_ADD
     return v.a + s;
   }
@@ -486,8 +521,8 @@ __device__ __forceinline__ double epi_store2(int r, bool both, double s0, double
   double c0 = 0.0, c1 = 0.0, q0 = 0.0, q1 = 0.0;
   const double y0 = epi_value<OP>(s0, u, e, c0, q0);
   const double y1 = epi_value<OP>(s1, w, e, c1, q1);
-  if (OP != EPI_RESID || e.y) st2(e.y, r, both, y0, y1);
-  if constexpr (OP == EPI_AXPBY || OP == EPI_RESID)
+  if ((OP != EPI_RESID && OP != EPI_POLY) || e.y) st2(e.y, r, both, y0, y1);
+  if constexpr (OP == EPI_AXPBY || OP == EPI_RESID || OP == EPI_POLY)
     if (e.copy_to) st2(e.copy_to, r, both, c0, c1);
   return both ? q0 + q1 : q0;
 }
@@ -2308,6 +2343,33 @@ int spmv_add(const mlamg_csr* A, const double* x, double* y, const int32_t* done
   ep.y = y;
   ep.done = done;
   return launch<EPI_ADD, false>(A, x, ep, s);
+}
+
+// The polynomial smoother's launches (poly.hip). poly_first: r = b - A x (r nullable) and
+// h = alpha * r, with xin set h = xin + alpha * r; h must not be x. poly_step: y = alpha * r + A h,
+// with acc set y = xin + (alpha * r + A h), xin NULL standing for an all-zero one; y must not be h.
+int poly_first(const mlamg_csr* A, const double* b, const double* x, double* r, double alpha,
+               const double* xin, double* h, const int32_t* done, hipStream_t s) {
+  Epi ep{};
+  ep.alpha = alpha;
+  ep.b = b;
+  ep.y = r;
+  ep.xin = xin;
+  ep.copy_to = h;
+  ep.done = done;
+  return launch<EPI_POLY, false>(A, x, ep, s);
+}
+
+int poly_step(const mlamg_csr* A, double alpha, const double* r, const double* h, bool acc,
+              const double* xin, double* y, const int32_t* done, hipStream_t s) {
+  Epi ep{};
+  ep.alpha = alpha;
+  ep.beta = acc ? 1.0 : 0.0;
+  ep.b = r;
+  ep.xin = acc ? xin : nullptr;
+  ep.y = y;
+  ep.done = done;
+  return launch<EPI_POLY, false>(A, h, ep, s);
 }
 
 // y += P e with P = (I - w D^-1 A) Agg applied factored (VERDICT r04 Next #5, opt-in): t = Agg e

@@ -175,6 +175,12 @@ SIGNATURES = {
     "mlamg_gs_sweep_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
     "mlamg_gs_mv_path": (c_int, [c_vp, c_int, P_i32]),
     "mlamg_gs_path": (c_int, [c_vp, c_int, P_i32]),
+    "mlamg_poly_create": (c_int, [c_vp, c_vp, c_int, c_vpp, c_vp]),
+    "mlamg_poly_destroy": (c_int, [c_vp]),
+    "mlamg_poly_info": (c_int, [c_vp, P_i64, P_int]),
+    "mlamg_poly_sweep": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "mlamg_poly_sweep_mv": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_int, c_vp]),
+    "mlamg_hier_set_level_polynomial": (c_int, [c_vp, c_int, c_vp, c_int]),
     "mlamg_dense_create": (c_int, [c_vp, c_vpp, c_vp]),
     "mlamg_dense_info": (c_int, [c_vp, P_int, P_i64]),
     "mlamg_dense_destroy": (c_int, [c_vp]),

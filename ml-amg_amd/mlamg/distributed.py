@@ -177,6 +177,10 @@ class DistributedHierarchy:
             raise ValueError("distributed cycle needs at least one level above the coarse solve")
         if (H.nu_pre, H.nu_post) != (1, 1):
             raise NotImplementedError("the distributed cycle is V(1,1)")
+        for i, L in enumerate(H.levels):
+            if getattr(L, "poly", None) is not None:
+                raise NotImplementedError(f"level {i} smooths with the polynomial (Chebyshev) "
+                                          "smoother, which the distributed cycle does not run")
         if any(L.seeds is None for L in H.levels):
             raise ValueError("hierarchy was not built by Hierarchy.build (seeds unknown)")
         self.H = H

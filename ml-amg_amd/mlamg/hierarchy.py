@@ -108,7 +108,8 @@ def _pyamg_empty_level(H, L, A_dev, agg, cpts, rounds, Bv, lvl, improve_iteratio
 
 class Level:
     __slots__ = ("A", "dinv", "P", "R", "Agg", "omega", "lam", "lanczos_iters", "n_seeds",
-                 "bf_sweeps", "seeds", "gs", "labels", "agg_col", "B", "sa_prolong")
+                 "bf_sweeps", "seeds", "gs", "labels", "agg_col", "B", "sa_prolong", "poly",
+                 "rho_A")
 
     def __init__(self, A):
         self.A = A
@@ -124,6 +125,8 @@ class Level:
         self.agg_col = None  # per-node aggregate column (int32 device tensor, -1 none)
         self.B = None  # near-nullspace candidate fitted at this level (pyamg_sa)
         self.sa_prolong = False  # P = (I - omega D^-1 A) Agg formed here (mlamg_sa_smoother)
+        self.poly = None  # polynomial smoother in use (multigrid.Polynomial), else None
+        self.rho_A = None  # rho(A) its Chebyshev coefficients were made for
 
 
 _PHASES = ("count", "alloc", "expand", "sort", "runsum", "emit", "finalize", "free")
@@ -163,6 +166,29 @@ def _aggregate_operator(agg, n):
     return aggregate_op_device(torch.as_tensor(lab.astype(np.int32)).to(_device()), k)
 
 
+def _smoother_spec(smoother):
+    """(name, options) of a pyamg-style smoother argument: a name or a (name, dict) pair."""
+    if isinstance(smoother, str):
+        return smoother, {}
+    if isinstance(smoother, (tuple, list)) and len(smoother) == 2 and isinstance(smoother[0], str):
+        return smoother[0], dict(smoother[1] or {})
+    raise ValueError(f"smoother must be a name or a (name, options) pair, got {smoother!r}")
+
+
+CHEBYSHEV_DEFAULTS = {"degree": 3, "iterations": 1, "lower_bound": 1.0 / 30.0, "upper_bound": 1.1}
+
+
+def _chebyshev_options(opts):
+    """pyamg's setup_chebyshev keywords with their defaults; anything else is refused."""
+    extra = set(opts) - set(CHEBYSHEV_DEFAULTS)
+    if extra:
+        raise NotImplementedError(f"chebyshev smoother options {sorted(extra)}")
+    o = dict(CHEBYSHEV_DEFAULTS, **opts)
+    if int(o["degree"]) < 1 or int(o["iterations"]) < 1:
+        raise ValueError("chebyshev degree and iterations must be >= 1")
+    return o
+
+
 def rhs_arg(b):
     """The right-hand side handed to mlamg_hier_vcycle: None when every entry of b is +0.0
     (bit pattern 0, so -0.0 does not count) — the reference's convergence-factor problems
@@ -194,16 +220,21 @@ class Hierarchy:
         self.coarse_gmres = False  # coarsest solve by GMRES + inner hierarchy (_make_coarse_gmres)
         self._breakdowns_seen = 0
         self._factored = {}
+        self.poly_iterations = 1
+        self._recipe_poly = None  # (per-level coefficients, iterations) of a Chebyshev recipe
 
     # ------------------------------------------------------------------ construction
     @classmethod
     def two_level(cls, A, P, omega=2.0 / 3.0, nu_pre=1, nu_post=1, dinv_w=None,
-                  smoother="jacobi", norm="residual", coarse="auto"):
+                  smoother="jacobi", norm="residual", coarse="auto", degree=3,
+                  smoother_rho="arnoldi"):
         """Two-level cycle with a given P: MLAMG.amg_2_v (ns/preconditioner/MLAMG.py:120-122,
         smoother='jacobi') or multigrid.amg_2_v (multigrid.py:111-210, smoother='gauss_seidel';
         norm='x' records ||x||_2 per cycle, the error_tol mode). coarse='dense' forces the
         dense inverse (up to DENSE_LIMIT rows) where 'auto' would take PCG; coarse='gmres'
-        the GMRES coarse solve (any A_c; Hierarchy._make_coarse_gmres)."""
+        the GMRES coarse solve (any A_c; Hierarchy._make_coarse_gmres). smoother='chebyshev':
+        pyamg's polynomial smoother of the given degree for rho(A) = smoother_rho ('arnoldi':
+        pyamg's approximate_spectral_radius, or a number), one iteration per sweep."""
         from .multigrid import GaussSeidel
         H = cls()
         H.jacobi_weight = omega
@@ -234,6 +265,10 @@ class Hierarchy:
             call("mlamg_hier_set_level_smoother", H.handle, 0, L.gs.handle)
             torch.cuda.synchronize()
             tm["gauss_seidel"] = time.perf_counter() - t0
+        elif smoother == "chebyshev":
+            H._set_chebyshev({"degree": degree}, smoother_rho)
+            torch.cuda.synchronize()
+            tm["chebyshev"] = time.perf_counter() - t0
         elif smoother != "jacobi":
             raise ValueError(f"unknown smoother {smoother!r}")
         H.timings = tm
@@ -644,7 +679,9 @@ class Hierarchy:
     @classmethod
     def pyamg_sa(cls, A, *, max_levels=10, max_coarse=10, theta=0.0, omega=4.0 / 3.0,
                  improve_iterations=4, rho="lanczos", B=None, fine_format="csr_stream",
-                 coarse_format="exact", verbose=False):
+                 coarse_format="exact", verbose=False,
+                 smoother=("block_gauss_seidel", {"sweep": "symmetric"}),
+                 smoother_rho="arnoldi"):
         """pyamg.aggregation.smoothed_aggregation_solver(A, max_levels=max_levels) with pyamg's
         defaults — the multilevel solver of the reference's PyAMG preconditioner
         (ns/preconditioner/PyAMG.py:94) — built on the GPU. Per level, while n > max_coarse
@@ -665,8 +702,20 @@ class Hierarchy:
         from numpy's global generator, as pyamg does), or a number / per-level list.
         pyamg is absent here: parity unpinned; every setup kernel is bitwise the oracle's
         restatement (oracle/oracle.c pyamg_*). Summation orders of pyamg's BSR products are not
-        restated (the Galerkin product sums over k ascending, as scipy's CSR/CSC kernels do)."""
+        restated (the Galerkin product sums over k ascending, as scipy's CSR/CSC kernels do).
+        smoother=('chebyshev', {'degree': 3, 'iterations': 1, 'lower_bound': 1/30,
+        'upper_bound': 1.1}) (or the bare name) smooths every level with pyamg's polynomial
+        smoother instead (presmoother = postsmoother = that pair; smoothing.setup_chebyshev):
+        per level the coefficients for rho(A) = smoother_rho — 'arnoldi' (default) pyamg's
+        approximate_spectral_radius(A), which draws from numpy's global generator, or a number /
+        per-level list. improve_candidates stays Gauss-Seidel."""
         from .multigrid import GaussSeidel
+        sm_name, sm_opts = _smoother_spec(smoother)
+        if sm_name == "chebyshev":
+            sm_opts = _chebyshev_options(sm_opts)
+        elif sm_name != "block_gauss_seidel" or sm_opts not in ({}, {"sweep": "symmetric"}):
+            raise NotImplementedError("smoother must be pyamg's default symmetric "
+                                      f"block_gauss_seidel or 'chebyshev', got {smoother!r}")
         if max_levels < 1:
             raise ValueError("max_levels must be >= 1")
         H = cls()
@@ -789,7 +838,9 @@ class Hierarchy:
         if H.levels:
             H.apply_formats(fine_format, coarse_format)
         t8 = time.perf_counter()
-        H._finalize_pinv()
+        H._finalize_pinv(gauss_seidel=sm_name != "chebyshev")
+        if sm_name == "chebyshev":
+            H._set_chebyshev(sm_opts, smoother_rho)
         torch.cuda.synchronize()
         tm["formats"] = t8 - t7
         tm["coarse_and_smoothers"] = time.perf_counter() - t8
@@ -797,9 +848,10 @@ class Hierarchy:
         H.timings = tm
         return H
 
-    def _finalize_pinv(self):
+    def _finalize_pinv(self, gauss_seidel=True):
         """pyamg's default coarse solver ('pinv': scipy.linalg.pinv of the dense A_c, applied as
-        a product) and symmetric block Gauss-Seidel V(1,1) smoothing on every level."""
+        a product) and symmetric block Gauss-Seidel V(1,1) smoothing on every level
+        (gauss_seidel=False: the caller sets another smoother)."""
         import scipy.linalg
         from .multigrid import GaussSeidel
         self.nu_pre = self.nu_post = 1
@@ -817,10 +869,73 @@ class Hierarchy:
             call("mlamg_hier_add_level", hh, L.A.handle, ptr(L.dinv), L.P.handle, L.R.handle)
         call("mlamg_hier_set_coarse", hh, self.Ac.handle, self.dense)
         call("mlamg_hier_set_smoothing", hh, 1, 1)
+        if not gauss_seidel:
+            return
         for i, L in enumerate(self.levels):
             if L.gs is None:
                 L.gs = GaussSeidel(L.A, "symmetric", block=True)
             call("mlamg_hier_set_level_smoother", hh, i, L.gs.handle)
+
+    def _set_chebyshev(self, opts, rho):
+        """Make the recipe's smoother pyamg's Chebyshev polynomial (setup_chebyshev per level)."""
+        from .multigrid import chebyshev_coefficients
+        o = _chebyshev_options(opts)
+        coeffs = []
+        for lvl, L in enumerate(self.levels):
+            if rho == "arnoldi":
+                from .strength import approximate_spectral_radius
+                r = approximate_spectral_radius(L.A)
+            else:
+                r = _level_item(rho, lvl) if isinstance(rho, (list, tuple)) else rho
+                if r is None:
+                    raise ValueError(f"no smoother_rho given for level {lvl}")
+            L.rho_A = float(r)
+            coeffs.append(chebyshev_coefficients(L.rho_A, int(o["degree"]),
+                                                 float(o["lower_bound"]),
+                                                 float(o["upper_bound"])))
+        self._recipe_poly = (coeffs, int(o["iterations"]))
+        self.set_polynomial_smoother(coeffs, int(o["iterations"]))
+
+    def set_polynomial_smoother(self, coefficients, iterations=1):
+        """Smooth with pyamg's relaxation.polynomial (multigrid.Polynomial) on every level of a
+        finalised hierarchy, whatever built it: each of the cycle's nu_pre / nu_post sweeps is
+        `iterations` iterations with `coefficients` (highest power first, no constant term;
+        multigrid.chebyshev_coefficients makes pyamg's) — one sequence for all levels or a list
+        of one sequence per level. Both cycle() and cycle_multi() take such levels, bitwise per
+        column. None removes them and restores the smoother the recipe set up (weighted Jacobi,
+        Gauss-Seidel, or pyamg_sa(smoother='chebyshev')'s own polynomials), bitwise. Returns
+        self."""
+        from .multigrid import Polynomial
+        if self.handle is None:
+            raise ValueError("the hierarchy is not finalised")
+        if coefficients is None:
+            if self._recipe_poly is not None:
+                return self.set_polynomial_smoother(*self._recipe_poly)
+            for i, L in enumerate(self.levels):
+                call("mlamg_hier_set_level_polynomial", self.handle, i, None, 1)
+                if L.gs is not None and self.recipe_gs(i):
+                    call("mlamg_hier_set_level_smoother", self.handle, i, L.gs.handle)
+                L.poly = None
+            self.poly_iterations = 1
+            return self
+        per_level = (isinstance(coefficients, (list, tuple)) and len(coefficients) > 0
+                     and np.ndim(coefficients[0]) == 1)
+        if per_level and len(coefficients) != len(self.levels):
+            raise ValueError(f"{len(coefficients)} coefficient sets for {len(self.levels)} levels")
+        if int(iterations) < 1:
+            raise ValueError("iterations must be >= 1")
+        new = [Polynomial(L.A, coefficients[i] if per_level else coefficients)
+               for i, L in enumerate(self.levels)]
+        for i, (L, S) in enumerate(zip(self.levels, new)):
+            call("mlamg_hier_set_level_polynomial", self.handle, i, S.handle, int(iterations))
+            L.poly = S  # the handle a level had is released only now
+        self.poly_iterations = int(iterations)
+        return self
+
+    def recipe_gs(self, level):
+        """Whether the recipe smooths `level` with its Gauss-Seidel handle (pyamg_sa keeps one
+        on level 0 for the candidate improvement even when it smooths with Chebyshev)."""
+        return self._recipe_poly is None and self.levels[level].gs is not None
 
     # coarsest solve: a dense inverse up to this many rows (its setup is O(n_c^3)), above it
     # PCG preconditioned by an inner hierarchy of the coarse operator (csrc/pcg.hip)
@@ -1189,9 +1304,17 @@ class Hierarchy:
     def describe(self):
         rows = []
         for i, L in enumerate(self.levels):
+            if L.poly is not None:
+                sm = (f"polynomial (degree {L.poly.coefficients.size}, "
+                      f"{self.poly_iterations} iteration(s) per sweep)")
+            elif L.gs is not None and self.recipe_gs(i):
+                sm = (("block " if L.gs.block else "") + f"gauss_seidel ({L.gs.sweep_dir})")
+            else:
+                sm = "weighted jacobi"
             rows.append({"level": i, "n": L.A.shape[0], "nnz": L.A.nnz,
                          "P_nnz": L.P.nnz, "omega": L.omega, "lambda_max": L.lam,
-                         "lanczos_iters": L.lanczos_iters, "bf_sweeps": L.bf_sweeps})
+                         "lanczos_iters": L.lanczos_iters, "bf_sweeps": L.bf_sweeps,
+                         "smoother": sm})
         rows.append({"level": len(self.levels), "n": self.Ac.shape[0], "nnz": self.Ac.nnz,
                      "coarse": "dense inverse" if self.dense is not None
                      else ("GMRES, inner SA hierarchy" if self.coarse_gmres

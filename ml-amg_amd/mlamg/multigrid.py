@@ -154,6 +154,62 @@ class GaussSeidel:
             self.handle = None
 
 
+def chebyshev_coefficients(rho, degree=3, lower_bound=1.0 / 30.0, upper_bound=1.1):
+    """The coefficients pyamg.relaxation.smoothing.setup_chebyshev hands to relaxation.polynomial
+    for an operator of spectral radius rho (rho(A), not rho(D^-1 A)):
+    -chebyshev_polynomial_coefficients(rho * lower_bound, rho * upper_bound, degree)[:-1], `degree`
+    numbers, highest power first (host numpy)."""
+    from .pyamg_compat.relaxation.chebyshev import chebyshev_polynomial_coefficients
+    rho = float(rho)
+    return -chebyshev_polynomial_coefficients(rho * lower_bound, rho * upper_bound,
+                                              int(degree))[:-1]
+
+
+class Polynomial:
+    """Polynomial smoother on a device operator: pyamg relaxation.polynomial's sweep with the
+    given coefficients (highest power first; chebyshev_coefficients makes pyamg's Chebyshev ones).
+    One iteration is len(coefficients) SpMV launches and nothing else (csrc/poly.hip)."""
+
+    def __init__(self, A_dev, coefficients):
+        c = np.ascontiguousarray(np.ravel(np.asarray(coefficients, dtype=np.float64)))
+        self.A = A_dev
+        self.coefficients = c
+        h = ctypes.c_void_p()
+        call("mlamg_poly_create", A_dev.handle, c.ctypes.data_as(ctypes.c_void_p), int(c.size),
+             ctypes.byref(h), stream_ptr())
+        self.handle = h
+
+    def sweep(self, x, b, iterations=1, x_is_zero=False):
+        """`iterations` iterations in place on x (cuda fp64; b likewise, or None for a zero
+        right-hand side). x_is_zero: x is not read and counts as all zero (the same bits as the
+        general sweep on a zero x, one pass over A fewer). A 2-D x is a block of k <= 64 vectors
+        (unit column stride): one mlamg_poly_sweep_mv, column j bitwise the sweep of column j."""
+        if getattr(x, "ndim", 1) == 2:
+            from .sparse import mv_block
+            n = self.A.shape[0]
+            k, ldx = mv_block(x, n, "x")
+            ldb = 0
+            if b is not None:
+                kb, ldb = mv_block(b, n, "b")
+                if kb != k:
+                    raise ValueError(f"b has {kb} columns, x has {k}")
+            call("mlamg_poly_sweep_mv", self.handle, ptr(x), ldx, ptr(b), ldb, k,
+                 int(iterations), int(bool(x_is_zero)), stream_ptr())
+            return x
+        call("mlamg_poly_sweep", self.handle, ptr(x), ptr(b), int(iterations),
+             int(bool(x_is_zero)), stream_ptr())
+        return x
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            try:
+                _lib.lib.mlamg_poly_destroy(h)
+            except Exception:
+                pass
+            self.handle = None
+
+
 def gauss_seidel(A, b, x, L=None, U=None, nu=2):
     """Gauss-Seidel, ns/lib/multigrid.py:58-90 (nu forward sweeps; L/U are ignored)."""
     A_dev = as_device(A)

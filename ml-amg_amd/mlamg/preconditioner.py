@@ -182,6 +182,9 @@ class MultilevelPC(MLAMG):
     candidate improvement by symmetric block Gauss-Seidel, fit_candidates, Jacobi-smoothed P
     with omega 4/3 / rho(D^-1 A), max_coarse 10, pinv coarse solve, symmetric block Gauss-Seidel
     V(1,1)); pyamg itself is absent, so parity is unpinned (bitwise the oracle's restatement).
+    Option '<prefix>pyamg_amg_smoother' = 'chebyshev' (default 'block_gauss_seidel') smooths with
+    pyamg's polynomial smoother of degree '<prefix>pyamg_amg_chebyshev_degree' (default 3)
+    instead: presmoother = postsmoother = ('chebyshev', {'degree': d}).
     Option '<prefix>pyamg_amg_recipe' = 'mlamg_sa' selects this package's own SA hierarchy
     instead (seeded Bellman-Ford aggregates, Jacobi smoothing, dense coarsest level).
     Apply (:118-120), `Amg.solve(b, tol=amg_rtol, accel='gmres' if amg_precondition_with_gmres
@@ -218,11 +221,21 @@ class MultilevelPC(MLAMG):
         prefix = ((pc.getOptionsPrefix() if hasattr(pc, "getOptionsPrefix") else "") or "")
         levels = opts.getInt(f"{prefix}{self._prefix}amg_max_levels", 10)
         recipe = opts.getString(f"{prefix}{self._prefix}amg_recipe", "pyamg_sa")
+        smoother = opts.getString(f"{prefix}{self._prefix}amg_smoother", "block_gauss_seidel")
+        degree = opts.getInt(f"{prefix}{self._prefix}amg_chebyshev_degree", 3)
+        if smoother not in ("block_gauss_seidel", "chebyshev"):
+            raise ValueError(f"unknown amg_smoother {smoother!r} (block_gauss_seidel, chebyshev)")
         if recipe == "pyamg_sa":
-            self.H = Hierarchy.pyamg_sa(A, max_levels=levels)
+            if smoother == "chebyshev":
+                self.H = Hierarchy.pyamg_sa(A, max_levels=levels,
+                                            smoother=("chebyshev", {"degree": degree}))
+            else:
+                self.H = Hierarchy.pyamg_sa(A, max_levels=levels)
         elif recipe == "mlamg_sa":
             self.H = Hierarchy.build(A, alpha=self.alpha, max_levels=levels,
                                      jacobi_weight=self.jacobi_weight)
+            if smoother == "chebyshev":
+                self.H._set_chebyshev({"degree": degree}, "arnoldi")
         else:
             raise ValueError(f"unknown amg_recipe {recipe!r} (pyamg_sa, mlamg_sa)")
 

@@ -71,7 +71,9 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
                                 keep=False, **kwargs):
     """pyamg's smoothed_aggregation_solver with its default recipe on the device (Hierarchy.
     pyamg_sa); returns a MultilevelSolver. Arguments other than the defaults, max_levels,
-    max_coarse, B (one candidate) and strength=('symmetric', {'theta': t}) raise
+    max_coarse, B (one candidate), strength=('symmetric', {'theta': t}) and presmoother ==
+    postsmoother == 'chebyshev' or ('chebyshev', {degree, iterations, lower_bound, upper_bound})
+    (pyamg's polynomial smoother, rho(A) by approximate_spectral_radius) raise
     NotImplementedError."""
     from ..hierarchy import Hierarchy
     from .multilevel import MultilevelSolver
@@ -85,10 +87,14 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
         omega = float(dict(smooth[1]).get("omega", omega))
     elif smooth != "jacobi":
         raise NotImplementedError("smooth must be 'jacobi' (pyamg's default)")
+    from ..hierarchy import _smoother_spec
+    pre, post = _smoother_spec(presmoother), _smoother_spec(postsmoother)
+    if pre != post:
+        raise NotImplementedError("presmoother and postsmoother must be the same")
     defaults_ok = (symmetry == "hermitian" and aggregate == "standard" and BH is None
                    and not diagonal_dominance and not keep
-                   and presmoother == postsmoother == ("block_gauss_seidel",
-                                                       {"sweep": "symmetric"}))
+                   and (pre[0] == "chebyshev"
+                        or pre == ("block_gauss_seidel", {"sweep": "symmetric"})))
     imp = improve_candidates[0] if isinstance(improve_candidates, (list, tuple)) else None
     iters = 0
     if imp is not None:
@@ -100,5 +106,6 @@ def smoothed_aggregation_solver(A, B=None, BH=None, symmetry="hermitian", streng
     if not (sp.isspmatrix_csr(A) or hasattr(A, "handle")):
         A = sp.csr_matrix(A)
     H = Hierarchy.pyamg_sa(A, max_levels=int(max_levels), max_coarse=int(max_coarse),
-                           theta=theta, omega=omega, improve_iterations=iters, B=B)
+                           theta=theta, omega=omega, improve_iterations=iters, B=B,
+                           smoother=pre)
     return MultilevelSolver(H)

@@ -1,2 +1,2 @@
 """pyamg.relaxation (4.x) subset."""
-from . import relaxation  # noqa: F401
+from . import chebyshev, relaxation  # noqa: F401

@@ -1,6 +1,7 @@
 """pyamg.relaxation.relaxation (4.x) subset on the device (csrc/gs.hip, bitwise the sequential
-sweeps): gauss_seidel as ns/lib/multigrid.py:175,184 call it, and block_gauss_seidel with 1 x 1
-blocks (the smoother of pyamg's smoothed_aggregation_solver). In place on x."""
+sweeps): gauss_seidel as ns/lib/multigrid.py:175,184 call it, block_gauss_seidel with 1 x 1
+blocks (the smoother of pyamg's smoothed_aggregation_solver), and polynomial (csrc/poly.hip:
+the sweep behind pyamg's 'chebyshev' smoother). In place on x."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -34,3 +35,22 @@ def block_gauss_seidel(A, x, b, iterations=1, sweep='forward', blocksize=1, Dinv
     if blocksize not in (None, 1) or Dinv is not None:
         raise NotImplementedError("1 x 1 blocks with pyamg's own Dinv only")
     _sweep(A, x, b, iterations, sweep, True)
+
+
+def polynomial(A, x, b, coefficients, iterations=1):
+    """pyamg polynomial (CSR): `iterations` times r = b - A x; h = c[0] r; h = c r + A h for the
+    other coefficients in turn; x += h. coefficients: highest power first, without the constant
+    term (pyamg's order)."""
+    import torch
+    from ...multigrid import Polynomial
+    from ...sparse import DeviceCSR
+    if not sp.isspmatrix_csr(A):
+        raise TypeError("expected csr_matrix")
+    if iterations < 1:
+        return
+    S = Polynomial(DeviceCSR.from_scipy(A), coefficients)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    xd = torch.as_tensor(np.ascontiguousarray(np.ravel(x), dtype=np.float64)).to(dev)
+    bd = torch.as_tensor(np.ascontiguousarray(np.ravel(b), dtype=np.float64)).to(dev)
+    S.sweep(xd, bd, int(iterations))
+    x[...] = np.reshape(xd.cpu().numpy(), np.shape(x))
