@@ -17,6 +17,9 @@ Mirrors the reference modules on the hot path:
   mlamg.loss            <- ns/model/loss.py      (amg_loss on a block of test vectors, fp64, and
                                                   its gradient with respect to P's values)
   mlamg.hierarchy       multilevel device hierarchy + V-cycle executor (precondition/solve)
+  mlamg.sa_setup        the per-level setup loop of Hierarchy.build
+  mlamg.pyamg_setup     the per-level setup loop of Hierarchy.pyamg_sa; the per-level rho rule
+  mlamg.autotune        SpMV format search of one operator (host rules; no torch, no library)
   mlamg.distributed     fine level row-partitioned over GPUs (RCCL halo exchange)
 
 Heavy submodules are imported lazily so `import mlamg` stays cheap.
@@ -29,7 +32,7 @@ __version__ = "0.1.0"
 
 _SUBMODULES = ("multigrid", "graph", "sparse", "strength", "gnn", "hierarchy",
                "preconditioner", "problems", "gridio", "distributed", "loss", "fitness", "_lib",
-               "interp", "greedy")
+               "interp", "greedy", "autotune", "sa_setup", "pyamg_setup")
 
 
 def __getattr__(name):

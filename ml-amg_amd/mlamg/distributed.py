@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, partition
+from . import autotune as tuner  # tune_local has an `autotune` argument
 from ._lib import _tol_arg, call, ptr, stream_ptr
 from .sparse import DeviceCSR
 
@@ -426,7 +427,6 @@ def tune_local(M_glob, M_loc, kind, autotune=True, family=None):
     M_glob None (a distributed setup: no global operator on the rank): `family` ('exact' or
     'vector', Hierarchy.apply_formats's rule on the global operator) names the family; the
     search starts from its first candidate."""
-    from .hierarchy import Hierarchy
     if M_glob is None:
         if family not in ("exact", "vector"):
             raise ValueError("tune_local without a global operator needs family='exact' or "
@@ -453,34 +453,17 @@ def tune_local(M_glob, M_loc, kind, autotune=True, family=None):
     y = torch.zeros(M_loc.shape[0], dtype=torch.float64, device="cuda")
     if kind == "A" and M_loc.shape[0] != M_loc.shape[1]:
         kind = "R"  # ghost columns: mlamg_residual is square-only, time y = A x instead
-    times = {}
-    if fmt == "vector":
-        cands = list(Hierarchy.VECTOR_CANDIDATES)
-    else:
-        cands = list(Hierarchy.EXACT_CANDIDATES)
-        if M_loc.nnz >= 16 * max(M_loc.shape[0], 1):
-            cands += list(Hierarchy.LONG_CANDIDATES)
-    # as Hierarchy.apply_formats: the global choice first, then the rest in order of their byte
-    # lower bound; a candidate that could not beat the best time even at LB_PEAK_BPS is skipped
-    # (a timing rule only: every candidate of the family computes the same bits)
-    lbs = {c: Hierarchy._lower_bound_us(M_loc, kind, c[0]) for c in cands}
-    cands.sort(key=lambda c: (c != (fmt, arg), lbs[c]))
-    pruned, refused = [], set()
-    for f, a in cands:
-        if (times and lbs[(f, a)] >= min(times.values())) or f in refused:
-            pruned.append(f"{f}/{a}")
-            continue
-        try:
-            times[f"{f}/{a}"] = Hierarchy._time_format(M_loc, f, a, x, y, kind=kind)
-        except _lib.MlamgError as e:
-            if e.code != _lib.MLAMG_EUNSUPPORTED:
-                raise
-            refused.add(f)
-    best = min(times, key=times.get)
+    cands = tuner.candidates_for(M_loc, "vector" if fmt == "vector" else "exact")
+    # The rules of this site, on top of the byte lower bound: the global choice is timed first,
+    # and a format one variant of which the local operator does not allow is not built again
+    # (ghost columns change what the encoders accept). No sigma or value-dictionary rule.
+    best, us, pruned = tuner.search(
+        cands, {c: tuner.lower_bound_us(M_loc, kind, c[0]) for c in cands},
+        lambda f, a: tuner.time_format(M_loc, f, a, x, y, kind=kind),
+        first=(fmt, arg), refuses_family=lambda f, a: True)
     f, a = best.split("/")
     M_loc.set_format(f, int(a))
-    return M_loc, {"chosen": best, "us": {k: round(v, 2) for k, v in times.items()},
-                   "pruned": pruned}
+    return M_loc, {"chosen": best, "us": us, "pruned": pruned}
 
 
 def sync_formats(H, world):

@@ -15,24 +15,23 @@ Seeds are RandomState(seed).permutation(n)[:k] bit for bit, the reference seedin
 MT19937 draws on the host, the shuffle's first k positions resolved on the device: graph.
 legacy_permutation); with sort_seeds=True (default for the multilevel solver) they are sorted so that
 coarse unknowns follow the fine ordering (better locality, contiguous ownership per GPU).
+
+This module holds the Hierarchy handle: its cycling and solver methods, the coarse-solver
+choice and two_level. The per-level setup loops live in mlamg/sa_setup.py (Hierarchy.build,
+the recipe above) and mlamg/pyamg_setup.py (Hierarchy.pyamg_sa), the SpMV format search that
+apply_formats runs in mlamg/autotune.py.
 """
 from __future__ import annotations
 
 import ctypes
-import math
-import statistics
 import time
 
 import numpy as np
-import scipy.sparse as sp
 import torch
 
-from . import _lib
+from . import _lib, autotune
 from ._lib import MLAMG_EUNSUPPORTED, MlamgError, _tol_arg, call, ptr, stream_ptr
-from .graph import (aggregate_op_device, bellman_ford_device, labels_to_columns,
-                    legacy_permutation, lloyd_cluster_device, modified_bellman_ford_device)
-from .multigrid import lambda_max_dinv_a
-from .sparse import DeviceCSR, _device, as_device, galerkin, to_device_vec
+from .sparse import DeviceCSR, as_device, csr_out, galerkin, to_device_vec
 
 STRENGTH_MODES = {"abs": 0, "invabs": 1, "unit": 2, "same": 3}
 
@@ -44,9 +43,7 @@ def strength(A_dev, mode="invabs", rho=None):
     if mode in ("evolution", "olson"):
         from .strength import evolution_device
         return evolution_device(A_dev, mode, rho=rho)
-    h = ctypes.c_void_p()
-    call("mlamg_strength", A_dev.handle, STRENGTH_MODES[mode], ctypes.byref(h), stream_ptr())
-    return DeviceCSR(h)
+    return csr_out("mlamg_strength", A_dev.handle, STRENGTH_MODES[mode])
 
 
 class CoarseSolveError(RuntimeError):
@@ -60,50 +57,6 @@ def csr_symmetric(M, rtol=0.0):
     ok = ctypes.c_int()
     call("mlamg_csr_symmetric", M.handle, float(rtol), ctypes.byref(ok), stream_ptr())
     return bool(ok.value)
-
-
-def _pyamg_empty_level(H, L, A_dev, agg, cpts, rounds, Bv, lvl, improve_iterations, rho,
-                       omega):
-    """pyamg_sa's level when standard aggregation finds no aggregate: an n x 1 empty AggOp
-    (pyamg's standard_aggregation return), T = 0, B_c = [0], P = 0 (n x 1), R = P^T, A_c =
-    [[0]]. The level keeps its symmetric block Gauss-Seidel smoother (pyamg still smooths it;
-    for the operators this happens on — no off-diagonal couplings — the sweep is an exact
-    solve). Appends L to H and returns (A_c, B_c)."""
-    from .multigrid import GaussSeidel
-    n = A_dev.shape[0]
-    dev = _device()
-    L.Agg = DeviceCSR.from_scipy(sp.csr_matrix((n, 1)))
-    L.agg_col = agg
-    L.seeds = cpts[:0]
-    L.n_seeds = 1
-    L.bf_sweeps = int(rounds.value)
-    if lvl == 0 and improve_iterations > 0:
-        L.gs = GaussSeidel(A_dev, "symmetric", block=True)
-        L.gs.sweep(Bv, torch.zeros_like(Bv), int(improve_iterations))
-    L.B = Bv
-    dinv = torch.empty(n, dtype=torch.float64, device=dev)
-    call("mlamg_diag_pinv", A_dev.handle, ptr(dinv), stream_ptr())
-    if rho == "lanczos":
-        # rho(D^-1 A) of an operator without off-diagonal couplings: 1 where a_ii != 0
-        L.lam = 1.0 if bool((dinv != 0).any()) else 0.0
-    elif rho == "arnoldi":  # pyamg's estimate (draws from numpy's global generator)
-        from .strength import approximate_spectral_radius
-        h = ctypes.c_void_p()
-        call("mlamg_csr_scale_rows", A_dev.handle, ptr(dinv), 0, ctypes.byref(h), stream_ptr())
-        L.lam = approximate_spectral_radius(DeviceCSR(h))
-    else:
-        r = _level_item(rho, lvl) if isinstance(rho, (list, tuple)) else rho
-        if r is None:
-            raise ValueError(f"no rho given for level {lvl}")
-        L.lam = float(r)
-    L.omega = omega / L.lam if L.lam else 0.0
-    L.P = DeviceCSR.from_scipy(sp.csr_matrix((n, 1)))
-    L.R = DeviceCSR.from_scipy(sp.csr_matrix((1, n)))
-    L.dinv = dinv
-    H.galerkin_s.append(0.0)
-    H.levels.append(L)
-    return (DeviceCSR.from_scipy(sp.csr_matrix((1, 1))),
-            torch.zeros(1, dtype=torch.float64, device=dev))
 
 
 class Level:
@@ -129,16 +82,6 @@ class Level:
         self.rho_A = None  # rho(A) its Chebyshev coefficients were made for
 
 
-_PHASES = ("count", "alloc", "expand", "sort", "runsum", "emit", "finalize", "free")
-
-
-def _setup_phases(reset=False):
-    """Accumulated SpGEMM phase wall times (ms) since the last reset (mlamg_setup_phase_times)."""
-    buf = (ctypes.c_double * len(_PHASES))()
-    call("mlamg_setup_phase_times", buf, len(_PHASES), int(bool(reset)))
-    return {k: round(float(v), 2) for k, v in zip(_PHASES, buf)}
-
-
 def _level_item(spec, lvl):
     """The level-`lvl` entry of a per-level specification (None, one item = level 0, or a
     list / tuple of items)."""
@@ -147,23 +90,6 @@ def _level_item(spec, lvl):
     if isinstance(spec, (list, tuple)):
         return spec[lvl] if lvl < len(spec) else None
     return spec if lvl == 0 else None
-
-
-def _aggregate_operator(agg, n):
-    """Agg (n x k, ones) on the device from a label vector (-1 = unaggregated) or a matrix."""
-    if isinstance(agg, DeviceCSR):
-        return agg
-    if sp.issparse(agg):
-        if agg.shape[0] != n:
-            raise ValueError(f"aggregate matrix has {agg.shape[0]} rows, the operator {n}")
-        A = sp.csr_matrix(agg, dtype=np.float64)
-        A.data[:] = 1.0
-        return DeviceCSR.from_scipy(A)
-    lab = np.asarray(agg.cpu().numpy() if isinstance(agg, torch.Tensor) else agg).astype(np.int64)
-    if lab.shape != (n,):
-        raise ValueError(f"aggregate labels must have shape ({n},), got {lab.shape}")
-    k = int(lab.max()) + 1 if lab.size else 0
-    return aggregate_op_device(torch.as_tensor(lab.astype(np.int32)).to(_device()), k)
 
 
 def _smoother_spec(smoother):
@@ -277,70 +203,6 @@ class Hierarchy:
         call("mlamg_hier_set_norm", H.handle, 0 if norm == "residual" else 1)
         return H
 
-    EXACT_CANDIDATES = (("csr_stream", 0), ("sell", 1), ("sell", 512), ("sorted", 0),
-                        ("sorted", 2), ("sell_dict", 1), ("sell_dict", 512), ("rowpat", 0))
-    LONG_CANDIDATES = (("long", 0),)
-    VECTOR_CANDIDATES = (("vector", 64), ("vector", 128), ("vector", 256), ("vector", 512))
-
-    # bytes read between two timed launches of the autotune, so each one starts with the
-    # operator and x out of the caches (L2 4 MB per XCD, MALL 256 MB) as in the cycle, where the
-    # other levels' streams pass in between; a read leaves no dirty lines to write back during
-    # the timed launch
-    FLUSH_BYTES = 512 << 20
-
-    @staticmethod
-    def _time_format(M, fmt, arg, x, y, reps=5, kind="A", flush=None):
-        """Median time of M's cycle operation in format fmt over `reps` launches, each after a
-        cache flush (a read of `flush`): the residual epilogue for A (r = b - A x, as in the
-        cycle; here b = y), y += M x for P, y = M x for R. Timing a launch repeated back to back
-        measures cache-resident operators (any operator up to the MALL's size), which
-        favoured formats that are not the fastest in the cycle."""
-        M.set_format(fmt, arg)
-        if kind == "A":
-            def op():
-                call("mlamg_residual", M.handle, ptr(y), ptr(x), ptr(y), None, stream_ptr())
-        elif kind == "P":
-            def op():
-                call("mlamg_prolong_add", M.handle, ptr(x), ptr(y), stream_ptr())
-        else:
-            def op():
-                M.matvec(x, out=y)
-        op()
-        s = torch.cuda.current_stream()
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-              for _ in range(reps)]
-        sink = torch.empty((), dtype=flush.dtype, device=flush.device) if flush is not None else None
-        for e0, e1 in ev:
-            if flush is not None:
-                torch.sum(flush, dim=0, out=sink)
-            e0.record(s)
-            op()
-            e1.record(s)
-        ev[-1][1].synchronize()
-        return statistics.median(e0.elapsed_time(e1) for e0, e1 in ev) * 1e3  # us
-
-    # Autotune pruning: the fewest bytes per stored nonzero a format can stream (sorted: 4-byte
-    # packed index + a 1-byte value code when the values fit a dictionary; sell_dict: a 2-byte
-    # code; rowpat: ~0, one byte per pair of rows; vector: 16-bit indices) at 7 TB/s: no
-    # candidate can beat that from a cold cache (the autotune reads 512 MB, twice the MALL,
-    # before each timed launch; 8 TB/s is the HBM peak, ~6.3 TB/s what streams reach, and the
-    # fastest cold kernel measured here runs at 3.7 TB/s of its bytes). A pruned candidate costs
-    # nothing but a timing chance: every format of the family computes the same bits. (Round 4:
-    # 8 -> 7 TB/s, so that e.g. SELL and CSR-stream are no longer built and timed for P_0 / R_0,
-    # whose sorted format already beats their bytes at 7 TB/s.)
-    FORMAT_MIN_BYTES_PER_NNZ = {"csr_stream": 12.0, "sell": 12.0, "sorted": 5.0, "sell_dict": 2.0,
-                                "rowpat": 0.0, "long": 12.0, "vector": 10.0}
-    LB_PEAK_BPS = 7e12
-    # a SELL / dictionary-SELL timed at more than this many times the best format so far skips
-    # its sigma-sorted (row-length-ordered) variant
-    SIGMA_SKIP_RATIO = 1.5
-
-    @classmethod
-    def _lower_bound_us(cls, M, kind, fmt):
-        n_rows, n_cols = M.shape
-        vec = 8.0 * (n_cols + n_rows + (n_rows if kind in ("A", "P") else 0))  # x, y (+ b / y in)
-        return (cls.FORMAT_MIN_BYTES_PER_NNZ[fmt] * M.nnz + vec) / cls.LB_PEAK_BPS * 1e6
-
     # operators whose mean row has at least this many entries use the lane-parallel CSR-vector
     # family (canonical order, one result for every width); shorter rows use the exact-order
     # (scipy) family. A rule on the matrix, not a timing: measured on the C4 hierarchy
@@ -348,18 +210,10 @@ class Hierarchy:
     # 34 us) up and lose below (A_2, 187 per row: 79 vs 54 us).
     VEC_MIN_MEAN_ROW = 256
 
-    # autotune decisions per operator signature (kind, shape, nnz, fingerprint of rows, columns
-    # and value bits, candidate family): a hierarchy rebuilt on the same operator (a dataset loop
-    # re-solving one grid, a distributed rank rebuilding rank 0's hierarchy) takes the same
-    # kernel without re-timing (VERDICT r04 Next #7). The choice is a timing decision only —
-    # every candidate of a family computes the same bits — so a stale entry costs speed, never
-    # a result. Bounded; cleared by clear_tune_cache().
-    _TUNE_CACHE = {}
-    TUNE_CACHE_MAX = 256
-
-    @classmethod
-    def clear_tune_cache(cls):
-        cls._TUNE_CACHE.clear()
+    @staticmethod
+    def clear_tune_cache():
+        """Forget the autotune's decisions: the next apply_formats times every operator."""
+        autotune.clear()
 
     def apply_formats(self, fine_format="autotune", coarse_format="auto", vec_min_row=None,
                       first_level=0):
@@ -384,76 +238,42 @@ class Hierarchy:
         vec_min_row = self.VEC_MIN_MEAN_ROW if vec_min_row is None else vec_min_row
         self.tuning = []
         dev = torch.device("cuda", torch.cuda.current_device())
-        flush = (torch.ones(self.FLUSH_BYTES // 8, dtype=torch.float64, device=dev)
+        flush = (torch.ones(autotune.FLUSH_BYTES // 8, dtype=torch.float64, device=dev)
                  if fine_format == "autotune" else None)
         for i, L in enumerate(self.levels):
             row = {}
             for name, M in (("A", L.A), ("P", L.P), ("R", L.R)):
-                if (i + first_level > 0 and coarse_format != "exact" and M.shape[0] <= (1 << 20)
-                        and M.nnz >= vec_min_row * M.shape[0]):
-                    cands = list(self.VECTOR_CANDIDATES)
-                else:
-                    cands = list(self.EXACT_CANDIDATES)
-                    if M.nnz >= 16 * M.shape[0]:
-                        cands += list(self.LONG_CANDIDATES)
                 if fine_format != "autotune":
                     M.set_format(fine_format if fine_format != "vector" else "auto_exact")
                     row[name] = {"chosen": M.get_format()[:2]}
                     continue
-                key = (name, M.shape, M.nnz, M.fingerprint(), tuple(cands))
-                hit = self._TUNE_CACHE.get(key)
-                if hit is not None:
-                    fmt, arg = hit["chosen"].split("/")
-                    M.set_format(fmt, int(arg))
-                    row[name] = dict(hit, cached=True)
-                    continue
-                x = torch.randn(M.shape[1], dtype=torch.float64, device=dev)
-                y = torch.zeros(M.shape[0], dtype=torch.float64, device=dev)
-                times = {}
-                # most compact formats first; a candidate whose bytes could not move in less
-                # than the best time so far, even at LB_PEAK_BPS, is neither built nor timed
-                # (a timing rule only: every candidate of the family computes the same bits)
-                lbs = {c: self._lower_bound_us(M, name, c[0]) for c in cands}
-                cands.sort(key=lambda c: lbs[c])
-                pruned = []
-                value_dict = False
-                refused = set()
-                for fmt, arg in cands:
-                    if times and lbs[(fmt, arg)] >= min(times.values()):
-                        pruned.append(f"{fmt}/{arg}")
-                        continue
-                    if fmt in refused or ((fmt, arg) == ("sorted", 2) and value_dict):
-                        # builds that would be refused: a dictionary-SELL or sorted limit of
-                        # one variant (too many column offsets or values, a row over a block)
-                        # holds for the others, and block dictionaries are refused when the
-                        # <= 256-value table applies (known from sorted/0). At C4 these
-                        # refused builds were half the autotune (0.46 of 0.99 s).
-                        pruned.append(f"{fmt}/{arg}")
-                        continue
-                    try:
-                        t = self._time_format(M, fmt, arg, x, y, kind=name, flush=flush)
-                        times[f"{fmt}/{arg}"] = t
-                        if (fmt, arg) == ("sorted", 0):
-                            value_dict = M.get_format()[1] == 1
-                        if fmt in ("sell", "sell_dict") and arg == 1 and \
-                                t > self.SIGMA_SKIP_RATIO * min(times.values()):
-                            # the sigma-sorted variant only reorders rows by length: it does not
-                            # close a gap this large to the best format (C4 A_0: its build
-                            # alone took 0.18 s, and it ran at 106 against rowpat's 56 us)
-                            refused.add(fmt)
-                    except MlamgError as e:  # format limits (e.g. sorted: row > 4096 nnz)
-                        if e.code != MLAMG_EUNSUPPORTED:
-                            raise
-                        if fmt in ("sell_dict", "sell") or (fmt, arg) == ("sorted", 0):
-                            refused.add(fmt)
-                best = min(times, key=times.get)
-                fmt, arg = best.split("/")
+                vector = (i + first_level > 0 and coarse_format != "exact"
+                          and M.shape[0] <= (1 << 20) and M.nnz >= vec_min_row * M.shape[0])
+                cands = autotune.candidates_for(M, "vector" if vector else "exact")
+
+                def search(name=name, M=M, cands=cands):
+                    x = torch.randn(M.shape[1], dtype=torch.float64, device=dev)
+                    y = torch.zeros(M.shape[0], dtype=torch.float64, device=dev)
+                    # This site's rules. Builds that would be refused are not tried (at C4 they
+                    # were half the autotune, 0.46 of 0.99 s): a SELL, dictionary-SELL or sorted
+                    # limit of one variant (too many column offsets or values, a row over a
+                    # block) holds for the others, and block dictionaries (sorted/2) are refused
+                    # when the <= 256-value table applies (known from sorted/0). A sigma-sorted
+                    # variant only reorders rows by length: it does not close a large gap to the
+                    # best format (C4 A_0: built in 0.18 s, it ran at 106 us, rowpat at 56).
+                    chosen, us, pruned = autotune.search(
+                        cands, {c: autotune.lower_bound_us(M, name, c[0]) for c in cands},
+                        lambda fmt, arg: autotune.time_format(M, fmt, arg, x, y, kind=name,
+                                                              flush=flush),
+                        refuses_family=lambda fmt, arg: (fmt in ("sell_dict", "sell")
+                                                         or (fmt, arg) == ("sorted", 0)),
+                        sigma_skip=autotune.SIGMA_SKIP_RATIO,
+                        value_dict=lambda: M.get_format()[1] == 1)
+                    return {"chosen": chosen, "us": us, "pruned": pruned}
+                row[name] = autotune.cached(
+                    (name, M.shape, M.nnz, M.fingerprint(), tuple(cands)), search)
+                fmt, arg = row[name]["chosen"].split("/")
                 M.set_format(fmt, int(arg))
-                row[name] = {"chosen": best, "us": {k: round(v, 2) for k, v in times.items()},
-                             "pruned": pruned}
-                if len(self._TUNE_CACHE) >= self.TUNE_CACHE_MAX:
-                    self._TUNE_CACHE.pop(next(iter(self._TUNE_CACHE)))
-                self._TUNE_CACHE[key] = row[name]
             self.tuning.append(row)
         self.attach_dinvs()
 
@@ -549,119 +369,18 @@ class Hierarchy:
             raise ValueError(f"unknown aggregation {aggregation!r}")
         if coarse_order not in ("seed", "sorted"):
             raise ValueError(f"coarse_order must be 'seed' or 'sorted', got {coarse_order!r}")
+        from . import sa_setup
         H = cls()
         H.jacobi_weight = jacobi_weight
         H.aggregation = aggregation
         H.coarse_order = coarse_order
         t_all = time.perf_counter()
-        A_dev = as_device(A)
-        tm = {"aggregation": 0.0, "lambda_max": 0.0, "prolongator": 0.0, "galerkin": 0.0,
-              "formats": 0.0, "dense": 0.0}
-        _setup_phases(reset=True)
-        H.galerkin_s = []
-        while True:
-            n = A_dev.shape[0]
-            if n <= max_coarse or len(H.levels) + 1 >= max_levels:
-                break
-            L = Level(A_dev)
-            lvl = len(H.levels)
-            P_given = _level_item(prolongators, lvl)
-            Agg_given = _level_item(aggregates, lvl)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            if P_given is None and Agg_given is None:
-                C = strength(A_dev, strength_mode)
-                k = int(math.ceil(alpha * n))
-                if isinstance(seed, (int, np.integer)) and 0 <= int(seed) < 2 ** 32:
-                    # RandomState(seed).permutation(n)[:k], bit for bit (device, csrc/seeds.hip)
-                    seeds = legacy_permutation(seed, n, k).cpu().numpy().astype(np.int64)
-                else:  # a seed numpy takes otherwise (None, an array, a generator's state)
-                    seeds = np.random.RandomState(seed).permutation(n)[:k]
-                if aggregation == "reference" and lvl == 0:
-                    # evaluate_dataset.py:80-90: push-order sweeps from the unsorted seeds
-                    seeds_dev = torch.as_tensor(seeds.astype(np.int32)).to(_device())
-                    _, lab, L.bf_sweeps = modified_bellman_ford_device(C, seeds_dev)
-                    if coarse_order == "sorted":
-                        seeds = np.sort(seeds)
-                        seeds_dev = torch.as_tensor(seeds.astype(np.int32)).to(_device())
-                    col = labels_to_columns(lab, seeds_dev)
-                    L.labels = lab
-                else:
-                    if sort_seeds:
-                        seeds = np.sort(seeds)
-                    seeds_dev = torch.as_tensor(seeds.astype(np.int32)).to(_device())
-                    if aggregation == "lloyd":
-                        _, col, _, L.bf_sweeps = lloyd_cluster_device(C, seeds_dev,
-                                                                      lloyd_maxiter, exact=False)
-                    else:
-                        _, lab, L.bf_sweeps = bellman_ford_device(C, seeds_dev)
-                        col = labels_to_columns(lab, seeds_dev)
-                        L.labels = lab
-                L.seeds = seeds
-                L.Agg = aggregate_op_device(col, k)
-                L.agg_col = col
-                L.n_seeds = k
-                del C
-            elif P_given is None:
-                L.Agg = _aggregate_operator(Agg_given, n)
-                L.n_seeds = L.Agg.shape[1]
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            if P_given is None or jacobi_weight == "sa":
-                if lvl == 0 and fine_format in ("autotune", "rowpat"):
-                    # Lanczos runs on the operator's own SpMV: a constant stencil gets its
-                    # row-pair format now (the autotune below reuses or replaces it)
-                    try:
-                        A_dev.set_format("rowpat")
-                    except _lib.MlamgError as e:
-                        if e.code != _lib.MLAMG_EUNSUPPORTED:
-                            raise
-                L.lam, L.lanczos_iters = lambda_max_dinv_a(A_dev, max_iter=lanczos_iter,
-                                                           tol=lanczos_tol)
-                L.omega = (4.0 / 3.0) / abs(L.lam)
-            t2 = time.perf_counter()
-            if P_given is None:
-                h = ctypes.c_void_p()
-                call("mlamg_sa_smoother", A_dev.handle, float(L.omega), ctypes.byref(h),
-                     stream_ptr())
-                S = DeviceCSR(h)
-                L.P = S @ L.Agg
-                L.sa_prolong = True
-                del S
-            else:
-                L.P = as_device(P_given)
-                if L.P.shape[0] != n:
-                    raise ValueError(f"level {lvl}: prolongator has {L.P.shape[0]} rows, "
-                                     f"the operator {n}")
-            if L.P.shape[1] >= n:
-                raise ValueError(f"level {lvl}: P has {L.P.shape[1]} columns for {n} rows "
-                                 "(no coarsening)")
-            L.R = L.P.transpose()
-            L.dinv = A_dev.diag_inv(L.omega if jacobi_weight == "sa" else jacobi_weight)
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
-            A_next = galerkin(L.R, A_dev, L.P)
-            torch.cuda.synchronize()
-            t4 = time.perf_counter()
-            tm["aggregation"] += t1 - t0
-            tm["lambda_max"] += t2 - t1
-            tm["prolongator"] += t3 - t2
-            tm["galerkin"] += t4 - t3
-            H.galerkin_s.append(round(t4 - t3, 4))
-            H.levels.append(L)
-            if verbose:
-                print(f"[mlamg] level {len(H.levels) - 1}: n={n} nnz={A_dev.nnz} "
-                      f"seeds={L.n_seeds} bf_sweeps={L.bf_sweeps} lam={L.lam} "
-                      f"({L.lanczos_iters} it) "
-                      f"P nnz={L.P.nnz} -> n_c={A_next.shape[0]} nnz_c={A_next.nnz} "
-                      f"[agg {t1 - t0:.2f}s lam {t2 - t1:.2f}s P {t3 - t2:.2f}s gal {t4 - t3:.2f}s]",
-                      flush=True)
-            A_dev = A_next
-        H.Ac = A_dev
-        # host-side view of the SpGEMM phases (Galerkin + SA products), then drop the cached
-        # scratch blocks (several GB at C4) so the cycle phase does not hold them
-        H.spgemm_phases_ms = _setup_phases(reset=True)
-        call("mlamg_scratch_trim", None)
+        tm = sa_setup.build_levels(
+            H, as_device(A), alpha=alpha, strength_mode=strength_mode, aggregation=aggregation,
+            max_coarse=max_coarse, max_levels=max_levels, jacobi_weight=jacobi_weight, seed=seed,
+            sort_seeds=sort_seeds, lanczos_tol=lanczos_tol, lanczos_iter=lanczos_iter,
+            lloyd_maxiter=lloyd_maxiter, fine_format=fine_format, verbose=verbose,
+            aggregates=aggregates, prolongators=prolongators, coarse_order=coarse_order)
         if not finalize:  # setup only (e.g. to take P for a two-level cycle)
             return H
         t5 = time.perf_counter()
@@ -709,7 +428,7 @@ class Hierarchy:
         per level the coefficients for rho(A) = smoother_rho — 'arnoldi' (default) pyamg's
         approximate_spectral_radius(A), which draws from numpy's global generator, or a number /
         per-level list. improve_candidates stays Gauss-Seidel."""
-        from .multigrid import GaussSeidel
+        from . import pyamg_setup
         sm_name, sm_opts = _smoother_spec(smoother)
         if sm_name == "chebyshev":
             sm_opts = _chebyshev_options(sm_opts)
@@ -722,118 +441,9 @@ class Hierarchy:
         H.recipe = "pyamg_sa"
         H.jacobi_weight = None
         t_all = time.perf_counter()
-        A_dev = as_device(A)
-        dev = _device()
-        n0 = A_dev.shape[0]
-        if B is None:
-            Bv = torch.ones(n0, dtype=torch.float64, device=dev)
-        else:
-            Bn = np.asarray(B, dtype=np.float64)
-            if Bn.size != n0:
-                raise NotImplementedError("one near-nullspace candidate (B of shape (n, 1))")
-            Bv = to_device_vec(Bn.reshape(-1)).clone()
-        tm = {"strength": 0.0, "aggregation": 0.0, "candidates": 0.0, "rho": 0.0,
-              "prolongator": 0.0, "galerkin": 0.0}
-        H.galerkin_s = []
-        while A_dev.shape[0] > max_coarse and len(H.levels) + 1 < max_levels:
-            n = A_dev.shape[0]
-            lvl = len(H.levels)
-            L = Level(A_dev)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            h = ctypes.c_void_p()
-            call("mlamg_symmetric_strength", A_dev.handle, float(theta), ctypes.byref(h),
-                 stream_ptr())
-            C = DeviceCSR(h)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            agg = torch.empty(n, dtype=torch.int32, device=dev)
-            cpts = torch.empty(n, dtype=torch.int32, device=dev)
-            k, rounds = ctypes.c_int64(), ctypes.c_int32()
-            call("mlamg_standard_aggregation", C.handle, ptr(agg), ptr(cpts), ctypes.byref(k),
-                 ctypes.byref(rounds), stream_ptr())
-            del C
-            k = int(k.value)
-            if k == 0:
-                # no node has an off-diagonal strength entry (a diagonal or fully decoupled
-                # operator): pyamg's standard_aggregation returns an n x 1 empty AggOp, so
-                # T = 0, B_c = 0, P = 0 and A_c = [[0]], whose pinv is 0 (a zero coarse
-                # correction); the level keeps its smoother
-                A_dev, Bv = _pyamg_empty_level(H, L, A_dev, agg, cpts, rounds, Bv, lvl,
-                                               improve_iterations, rho, omega)
-                continue
-            L.Agg = aggregate_op_device(agg, k)
-            L.agg_col = agg
-            L.seeds = cpts[:k]
-            L.n_seeds = k
-            L.bf_sweeps = int(rounds.value)
-            t2 = time.perf_counter()
-            if lvl == 0 and improve_iterations > 0:
-                # the same symmetric block sweep later smooths this level: one handle
-                L.gs = GaussSeidel(A_dev, "symmetric", block=True)
-                L.gs.sweep(Bv, torch.zeros_like(Bv), int(improve_iterations))
-            L.B = Bv
-            h = ctypes.c_void_p()
-            Bc = torch.empty(k, dtype=torch.float64, device=dev)
-            call("mlamg_fit_candidates", L.Agg.handle, ptr(Bv), 1e-10, ctypes.byref(h), ptr(Bc),
-                 stream_ptr())
-            T = DeviceCSR(h)
-            torch.cuda.synchronize()
-            t3 = time.perf_counter()
-            dinv = torch.empty(n, dtype=torch.float64, device=dev)
-            call("mlamg_diag_pinv", A_dev.handle, ptr(dinv), stream_ptr())
-            h = ctypes.c_void_p()
-            call("mlamg_csr_scale_rows", A_dev.handle, ptr(dinv), 0, ctypes.byref(h),
-                 stream_ptr())
-            DinvA = DeviceCSR(h)
-            if rho == "lanczos":
-                # pyamg's own estimate is a 15-step Arnoldi value to a relative 1e-2
-                # (approximate_spectral_radius's tol); 1e-6 is far tighter
-                lam, L.lanczos_iters = lambda_max_dinv_a(A_dev, tol=1e-6)
-                L.lam = abs(lam)
-            elif rho == "arnoldi":
-                from .strength import approximate_spectral_radius
-                L.lam = approximate_spectral_radius(DinvA)
-            else:
-                r = _level_item(rho, lvl) if isinstance(rho, (list, tuple)) else rho
-                if r is None:
-                    raise ValueError(f"no rho given for level {lvl}")
-                L.lam = float(r)
-            t4 = time.perf_counter()
-            L.omega = omega / L.lam
-            h = ctypes.c_void_p()
-            cvec = torch.full((n,), L.omega, dtype=torch.float64, device=dev)
-            call("mlamg_csr_scale_rows", DinvA.handle, ptr(cvec), 0, ctypes.byref(h),
-                 stream_ptr())
-            DinvA = DeviceCSR(h)
-            M = DinvA @ T
-            del DinvA
-            h = ctypes.c_void_p()
-            call("mlamg_csr_sub", T.handle, M.handle, ctypes.byref(h), stream_ptr())
-            L.P = DeviceCSR(h)
-            del M, T
-            L.R = L.P.transpose()
-            L.dinv = dinv
-            torch.cuda.synchronize()
-            t5 = time.perf_counter()
-            A_next = galerkin(L.R, A_dev, L.P)
-            torch.cuda.synchronize()
-            t6 = time.perf_counter()
-            for key, dt in (("strength", t1 - t0), ("aggregation", t2 - t1),
-                            ("candidates", t3 - t2), ("rho", t4 - t3),
-                            ("prolongator", t5 - t4), ("galerkin", t6 - t5)):
-                tm[key] += dt
-            H.galerkin_s.append(round(t6 - t5, 4))
-            H.levels.append(L)
-            if verbose:
-                print(f"[mlamg pyamg_sa] level {lvl}: n={n} nnz={A_dev.nnz} aggregates={k} "
-                      f"rounds={L.bf_sweeps} rho={L.lam:.6g} P nnz={L.P.nnz} -> "
-                      f"n_c={A_next.shape[0]} nnz_c={A_next.nnz}", flush=True)
-            A_dev = A_next
-            Bv = Bc
-        H.Ac = A_dev
-        H.B_coarse = Bv
-        call("mlamg_scratch_trim", None)
+        tm = pyamg_setup.build_levels(
+            H, as_device(A), B, max_levels=max_levels, max_coarse=max_coarse, theta=theta,
+            omega=omega, improve_iterations=improve_iterations, rho=rho, verbose=verbose)
         t7 = time.perf_counter()
         if H.levels:
             H.apply_formats(fine_format, coarse_format)
@@ -854,7 +464,6 @@ class Hierarchy:
         (gauss_seidel=False: the caller sets another smoother)."""
         import scipy.linalg
         from .multigrid import GaussSeidel
-        self.nu_pre = self.nu_post = 1
         Ad = self.Ac.to_scipy().toarray()
         Pinv = np.ascontiguousarray(scipy.linalg.pinv(Ad), dtype=np.float64)
         self.coarse_pinv = Pinv
@@ -862,34 +471,24 @@ class Hierarchy:
         call("mlamg_dense_create_matrix", Pinv.ctypes.data_as(ctypes.c_void_p),
              int(Pinv.shape[0]), ctypes.byref(h), stream_ptr())
         self.dense = h
-        hh = ctypes.c_void_p()
-        call("mlamg_hier_create", ctypes.byref(hh))
-        self.handle = hh
-        for L in self.levels:
-            call("mlamg_hier_add_level", hh, L.A.handle, ptr(L.dinv), L.P.handle, L.R.handle)
-        call("mlamg_hier_set_coarse", hh, self.Ac.handle, self.dense)
-        call("mlamg_hier_set_smoothing", hh, 1, 1)
+        self._assemble(1, 1)
         if not gauss_seidel:
             return
         for i, L in enumerate(self.levels):
             if L.gs is None:
                 L.gs = GaussSeidel(L.A, "symmetric", block=True)
-            call("mlamg_hier_set_level_smoother", hh, i, L.gs.handle)
+            call("mlamg_hier_set_level_smoother", self.handle, i, L.gs.handle)
 
     def _set_chebyshev(self, opts, rho):
         """Make the recipe's smoother pyamg's Chebyshev polynomial (setup_chebyshev per level)."""
         from .multigrid import chebyshev_coefficients
+        from .pyamg_setup import level_rho
+        from .strength import approximate_spectral_radius
         o = _chebyshev_options(opts)
         coeffs = []
         for lvl, L in enumerate(self.levels):
-            if rho == "arnoldi":
-                from .strength import approximate_spectral_radius
-                r = approximate_spectral_radius(L.A)
-            else:
-                r = _level_item(rho, lvl) if isinstance(rho, (list, tuple)) else rho
-                if r is None:
-                    raise ValueError(f"no smoother_rho given for level {lvl}")
-            L.rho_A = float(r)
+            L.rho_A = float(level_rho(
+                rho, lvl, {"arnoldi": lambda: approximate_spectral_radius(L.A)}, "smoother_rho"))
             coeffs.append(chebyshev_coefficients(L.rho_A, int(o["degree"]),
                                                  float(o["lower_bound"]),
                                                  float(o["upper_bound"])))
@@ -967,7 +566,6 @@ class Hierarchy:
     def _finalize(self, nu_pre, nu_post, dense_max=None, coarse_rtol=None, coarse=None):
         """coarse: None chooses (dense inverse up to dense_max rows; above, PCG for a symmetric
         A_c, else the dense inverse up to DENSE_LIMIT rows, else GMRES); 'gmres' forces GMRES."""
-        self.nu_pre, self.nu_post = nu_pre, nu_post
         dense_max = self.DENSE_MAX if dense_max is None else dense_max
         n_c = self.Ac.shape[0]
         use_gmres = coarse == "gmres"
@@ -987,6 +585,13 @@ class Hierarchy:
             self.dense = h
         else:
             self._make_coarse_pcg(self.COARSE_RTOL if coarse_rtol is None else coarse_rtol)
+        self._assemble(nu_pre, nu_post)
+
+    def _assemble(self, nu_pre, nu_post):
+        """Create the mlamg_hier handle: the levels, the coarse solver this hierarchy holds (a
+        dense inverse or pinv matrix, PCG, or GMRES with its four parameters) and the smoothing
+        counts."""
+        self.nu_pre, self.nu_post = nu_pre, nu_post
         hh = ctypes.c_void_p()
         call("mlamg_hier_create", ctypes.byref(hh))
         self.handle = hh
@@ -1110,11 +715,30 @@ class Hierarchy:
     def solve(self, b, x0=None, tol=1e-8, maxiter=500, return_history=False):
         """Stationary V-cycle iteration until ||b - A x||_2 <= tol (absolute, MLAMG.py:194);
         tol=None runs all maxiter cycles."""
-        bd = to_device_vec(b)
-        xd = torch.zeros_like(bd) if x0 is None else to_device_vec(x0).clone()
+        _, bd, xd = self._krylov_in(b, x0)
         hist = self.cycle(bd, xd, maxiter, tol=tol)
         x = xd.cpu().numpy() if not isinstance(b, torch.Tensor) else xd
         return (x, hist) if return_history else x
+
+    def _krylov_in(self, b, x0, in_place=False):
+        """(A, b on the device, the iterate: a copy of x0, or zeros) for a solver wrapper;
+        in_place takes a cuda fp64 b as it is (e.g. a column slice of a wider tensor)."""
+        A = self.levels[0].A if self.levels else self.Ac
+        if in_place and isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float64:
+            bd = b
+        else:
+            bd = to_device_vec(b)
+        if x0 is None:
+            xd = torch.zeros(tuple(bd.shape), dtype=torch.float64, device=bd.device)
+        else:
+            xd = to_device_vec(x0).clone()
+        return A, bd, xd
+
+    def _krylov_out(self, b, xd):
+        """The iterate as a GMRES wrapper returns it (numpy for a numpy b, the tensor for a
+        tensor b), after the check for a coarse solve that broke down in the preconditioner."""
+        self.check_coarse()
+        return xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
 
     def gmres(self, b, x0=None, rtol=1e-5, restart=20, maxiter=None, return_info=False):
         """GMRES on A x = b preconditioned by one V-cycle of this hierarchy (mlamg_gmres:
@@ -1127,18 +751,14 @@ class Hierarchy:
         if getattr(b, "ndim", 1) == 2:
             return self.gmres_multi(b, x0, rtol=rtol, restart=restart, maxiter=maxiter,
                                     return_info=return_info)
-        A = self.levels[0].A if self.levels else self.Ac
-        bd = to_device_vec(b)
-        xd = torch.zeros_like(bd) if x0 is None else to_device_vec(x0).clone()
-        n = bd.numel()
+        A, bd, xd = self._krylov_in(b, x0)
         cap = 4096
         hist = (ctypes.c_double * cap)()
         info, inner = ctypes.c_int(), ctypes.c_int()
         self._solve_call("mlamg_gmres", A.handle, self.handle, ptr(bd), ptr(xd), float(rtol),
                          int(restart), int(maxiter or 0), int(x0 is None), ctypes.byref(info),
                          ctypes.byref(inner), hist, cap, stream_ptr())
-        self.check_coarse()  # a broken-down coarse solve inside the preconditioner
-        x = xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
+        x = self._krylov_out(b, xd)
         if not return_info:
             return x
         k = min(inner.value, cap)
@@ -1157,17 +777,11 @@ class Hierarchy:
         cycle, with cycle_multi's coarse solves and refusals: Gauss-Seidel levels need
         enable_block_gauss_seidel() first, 'vector'-format operators enable_block_vector()."""
         from .sparse import mv_block
-        A = self.levels[0].A if self.levels else self.Ac
+        A, Bd, Xd = self._krylov_in(B, X0, in_place=True)
         n = A.shape[0]
-        as_tensor = isinstance(B, torch.Tensor)
-        Bd = B if as_tensor and B.is_cuda and B.dtype == torch.float64 else to_device_vec(B)
         k, ldb = mv_block(Bd, n, "B")
-        if X0 is None:
-            Xd = torch.zeros((n, k), dtype=torch.float64, device=Bd.device)
-        else:
-            Xd = to_device_vec(X0).clone()
-            if tuple(Xd.shape) != (n, k):
-                raise ValueError(f"X0 has shape {tuple(Xd.shape)}, expected {(n, k)}")
+        if tuple(Xd.shape) != (n, k):
+            raise ValueError(f"X0 has shape {tuple(Xd.shape)}, expected {(n, k)}")
         cap = 4096
         hist = np.zeros((cap, k), dtype=np.float64)
         info = np.zeros(k, dtype=np.int32)
@@ -1177,8 +791,7 @@ class Hierarchy:
                          float(rtol), int(restart), int(maxiter or 0), int(X0 is None),
                          info.ctypes.data_as(P_i32), inner.ctypes.data_as(P_i32),
                          hist.ctypes.data, cap, stream_ptr())
-        self.check_coarse()  # a broken-down coarse solve inside the preconditioner
-        X = Xd if as_tensor else Xd.cpu().numpy()
+        X = self._krylov_out(B, Xd)
         if not return_info:
             return X
         return X, {"info": info, "inner_iters": inner,
@@ -1191,17 +804,14 @@ class Hierarchy:
         Returns x (numpy in -> numpy out, tensor in -> tensor out), plus {"info", "iters",
         "residuals"} (preconditioned residual norms: initial, per step, final) with
         return_info=True."""
-        A = self.levels[0].A if self.levels else self.Ac
-        bd = to_device_vec(b)
-        xd = torch.zeros_like(bd) if x0 is None else to_device_vec(x0).clone()
+        A, bd, xd = self._krylov_in(b, x0)
         cap = 4096
         hist = (ctypes.c_double * cap)()
         info, iters = ctypes.c_int(), ctypes.c_int()
         self._solve_call("mlamg_gmres_householder", A.handle, self.handle, ptr(bd), ptr(xd),
                          float(tol), int(maxiter or 0), int(x0 is None), ctypes.byref(info),
                          ctypes.byref(iters), hist, cap, stream_ptr())
-        self.check_coarse()
-        x = xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
+        x = self._krylov_out(b, xd)
         if not return_info:
             return x
         # recorded: the initial norm, one per step except the last (the budget's last step, or
@@ -1274,14 +884,8 @@ class Hierarchy:
         Gauss-Seidel levels, pyamg_sa's for one, needs enable_block_gauss_seidel() first, one
         with 'vector'-format operators, build()'s default on long-row coarse levels,
         enable_block_vector())."""
-        if getattr(b, "ndim", 1) == 2:
-            bd = to_device_vec(b)
-            xd = torch.zeros_like(bd)
-            self.cycle_multi(bd, xd, 1, history=False)
-            return xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
-        bd = to_device_vec(b)
-        xd = torch.zeros_like(bd)
-        self.cycle(bd, xd, 1, history=False)
+        _, bd, xd = self._krylov_in(b, None)
+        (self.cycle_multi if getattr(b, "ndim", 1) == 2 else self.cycle)(bd, xd, 1, history=False)
         return xd if isinstance(b, torch.Tensor) else xd.cpu().numpy()
 
     def cycle_bytes(self, stored=False):

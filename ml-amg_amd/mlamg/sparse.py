@@ -216,9 +216,7 @@ class DeviceCSR:
         return out
 
     def transpose(self):
-        h = ctypes.c_void_p()
-        call("mlamg_transpose", self.handle, ctypes.byref(h), stream_ptr())
-        return DeviceCSR(h)
+        return csr_out("mlamg_transpose", self.handle)
 
     @property
     def T(self):
@@ -226,9 +224,7 @@ class DeviceCSR:
 
     def __matmul__(self, other):
         if isinstance(other, DeviceCSR):
-            h = ctypes.c_void_p()
-            call("mlamg_spgemm", self.handle, other.handle, ctypes.byref(h), stream_ptr())
-            return DeviceCSR(h)
+            return csr_out("mlamg_spgemm", self.handle, other.handle)
         if isinstance(other, torch.Tensor):
             return self.matmat(other) if other.ndim == 2 else self.matvec(other)
         return NotImplemented
@@ -295,15 +291,21 @@ class DeviceCSR:
         return f"DeviceCSR(shape={self.shape}, nnz={self.nnz})"
 
 
+def csr_out(name, *args):
+    """The DeviceCSR made by the C-ABI entry `name`, whose last two arguments — after `args` —
+    are the out-handle and the stream."""
+    h = ctypes.c_void_p()
+    call(name, *args, ctypes.byref(h), stream_ptr())
+    return DeviceCSR(h)
+
+
 def as_device(A):
     return A if isinstance(A, DeviceCSR) else DeviceCSR.from_scipy(A)
 
 
 def galerkin(R, A, P):
     """A_c = (R@A)@P on the device (ns/lib/multigrid.py:165 `P.T@A@P`)."""
-    h = ctypes.c_void_p()
-    call("mlamg_galerkin", R.handle, A.handle, P.handle, ctypes.byref(h), stream_ptr())
-    return DeviceCSR(h)
+    return csr_out("mlamg_galerkin", R.handle, A.handle, P.handle)
 
 
 def to_device_vec(x, dtype=torch.float64):

@@ -1,12 +1,6 @@
-"""CPU: the autotune's pruning bound (Hierarchy._lower_bound_us) — the most compact formats come
+"""CPU: the autotune's pruning bound (autotune.lower_bound_us) — the most compact formats come
 first and no candidate is skipped unless its bytes could not move in the best time so far."""
-import os
-import sys
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "ml-amg_amd", "mlamg", "libmlamg_hip.so")
+from mlamg.autotune import lower_bound_us
 
 
 class _Op:
@@ -15,12 +9,9 @@ class _Op:
         self.nnz = nnz
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="libmlamg_hip.so not built")
 def test_lower_bound_order_and_values():
-    sys.path.insert(0, os.path.join(ROOT, "ml-amg_amd"))
-    from mlamg.hierarchy import Hierarchy
     A0 = _Op(10077696, 10077696, 70263936)  # C4 fine operator
-    lb = {f: Hierarchy._lower_bound_us(A0, "A", f)
+    lb = {f: lower_bound_us(A0, "A", f)
           for f in ("rowpat", "sell_dict", "sorted", "csr_stream", "sell", "long")}
     assert lb["rowpat"] < lb["sell_dict"] < lb["sorted"] < lb["csr_stream"] == lb["sell"]
     # x, y and b at 7 TB/s: 34.6 us; CSR adds 12 B per nonzero: 120.5 us more
@@ -31,4 +22,4 @@ def test_lower_bound_order_and_values():
     assert lb["rowpat"] < 44.0 and lb["csr_stream"] < 160.0 and lb["sorted"] < 100.0
     assert lb["sell_dict"] < 77.0
     P = _Op(1008, 10078, 878932)  # R_3
-    assert Hierarchy._lower_bound_us(P, "R", "vector") < 8.0
+    assert lower_bound_us(P, "R", "vector") < 8.0

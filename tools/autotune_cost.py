@@ -14,7 +14,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "ml-amg_amd")]
 
 import torch  # noqa: E402
 
-from mlamg import problems  # noqa: E402
+from mlamg import autotune, problems  # noqa: E402
 from mlamg.hierarchy import Hierarchy  # noqa: E402
 from mlamg.sparse import DeviceCSR  # noqa: E402
 
@@ -28,7 +28,7 @@ def main():
     H = Hierarchy.build(A, alpha=0.1, max_coarse=2000, aggregation="reference",
                         coarse_order="sorted", finalize=False)
     rows = []
-    orig_set, orig_time = DeviceCSR.set_format, Hierarchy._time_format
+    orig_set, orig_time = DeviceCSR.set_format, autotune.time_format
     cur = {}
 
     def set_format(self, fmt, vec_width=0):
@@ -56,13 +56,13 @@ def main():
         return us
 
     DeviceCSR.set_format = set_format
-    Hierarchy._time_format = staticmethod(time_format)
+    autotune.time_format = time_format
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     H.apply_formats("autotune", "auto")
     torch.cuda.synchronize()
     total = time.perf_counter() - t0
-    DeviceCSR.set_format, Hierarchy._time_format = orig_set, staticmethod(orig_time)
+    DeviceCSR.set_format, autotune.time_format = orig_set, orig_time
     for r in rows:
         print(r)
     print({"apply_formats_s": round(total, 3),

@@ -8,7 +8,7 @@ mlamg_spmv launches on the same handle in the csr_stream format (one column vect
 Cycle: Hierarchy.cycle_multi against k single Hierarchy.cycle_async calls on a
 coarse_format="exact", fine_format="csr_stream" hierarchy.
 
-Timing as the format autotune does (Hierarchy._time_format): a warm-up, then per repetition a
+Timing as the format autotune does (mlamg.autotune.time_format): a warm-up, then per repetition a
 cache flush (a 512 MB read), an event, the launches, an event; the median over the repetitions.
 The byte model of one SpMM is 12 nnz + 4 (n + 1) + 8 k (n_cols + n_rows); `model_fraction` is
 that over 8 TB/s, divided by the measured time.

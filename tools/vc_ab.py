@@ -21,19 +21,19 @@ def main():
     ap.add_argument("--n", type=int, default=216)
     ap.add_argument("--tag", default=os.environ.get("MLAMG_LIB", "default"))
     args = ap.parse_args()
-    from mlamg import problems
+    from mlamg import autotune, problems
     from mlamg.hierarchy import Hierarchy
     A = problems.poisson_3d_7pt(args.n)
     H = Hierarchy.build(A, alpha=0.1, max_coarse=2000, aggregation="reference",
                         coarse_order="sorted", finalize=False)
     M = H.levels[1].A
     dev = torch.device("cuda")
-    flush = torch.ones(Hierarchy.FLUSH_BYTES // 8, dtype=torch.float64, device=dev)
+    flush = torch.ones(autotune.FLUSH_BYTES // 8, dtype=torch.float64, device=dev)
     x = torch.randn(M.shape[1], dtype=torch.float64, device=dev)
     y = torch.zeros(M.shape[0], dtype=torch.float64, device=dev)
     out = {"tag": os.path.basename(args.tag), "rows": M.shape[0], "nnz": M.nnz}
     for fmt, arg in (("sorted", 0), ("sorted", 2), ("sorted", 0), ("sorted", 2)):
-        t = Hierarchy._time_format(M, fmt, arg, x, y, reps=9, kind="A", flush=flush)
+        t = autotune.time_format(M, fmt, arg, x, y, reps=9, kind="A", flush=flush)
         out.setdefault(f"{fmt}/{arg}_us", []).append(round(t, 2))
         out[f"{fmt}/{arg}_bytes"] = M.format_bytes()
     v = M.to_scipy().data
