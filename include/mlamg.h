@@ -315,6 +315,38 @@ int mlamg_gnn_topk_seg(const float* scores, const int64_t* seg_ptr, const int64_
                        const int64_t* k_ptr, const int64_t* k_ptr_host, int64_t nb, float* vec,
                        int32_t* idx, void* stream);
 
+/* A population stack (FullAggNet.forward_population: every individual of the genetic algorithm in
+ * one pass): `members` equal copies of one base stack end to end. Member p owns rows
+ * [p M, (p + 1) M) and edges [p E, (p + 1) E) (M, n, E below are PER MEMBER); node and edge ids in
+ * src, tgt, tptr (members * n + 1 entries) and teid are ids of the whole stack; member p's tensor
+ * of a parameter lies at ptr + p * pstride floats, one pstride for every weight argument of a
+ * call (all parameters are views into one (members, total) matrix; pstride = 0: shared weights).
+ * Member p's part of every output is bitwise what the single entry writes when run on that
+ * member's rows or edges alone with member p's tensors: the single entries are these kernels
+ * with members = 1, a workgroup works for one member, and no tile of rows or edges straddles two.
+ * Limits, beyond the single entry's own (EINVAL before any launch, outputs untouched):
+ * 1 <= members <= 65535, pstride >= 0, members * M, members * n and members * E < 2^31 - 1. */
+/* mlamg_gnn_linear per member: W[N][K] and b[N] (nullable) are member-indexed. */
+int mlamg_gnn_linear_pop(const float* X, int64_t M, int members, int K, const float* W,
+                         const float* b, int64_t pstride, int N, int act, float beta,
+                         const float* R, int rc, float* Y, void* stream);
+/* mlamg_gnn_nnconv per member: L1, c1, L2, c2, L3, c3 and bias are member-indexed; root, R, Y
+ * and msg_tmp[members * E * Fout] cover the whole stack. NULL tptr or X, or a NULL edge or
+ * edge-network argument with E > 0, is refused too. */
+int mlamg_gnn_nnconv_pop(const int32_t* tptr, const int32_t* teid, const int32_t* src,
+                         const float* ea, int64_t E, int members, int fe, const float* L1,
+                         const float* c1, const float* L2, const float* c2, const float* L3,
+                         const float* c3, int64_t pstride, const float* X, int64_t n, int Fin,
+                         int Fout, const float* root, const float* bias, int act, const float* R,
+                         int rc, float* msg_tmp, float* Y, void* stream);
+/* mlamg_gnn_edge_mlp per member: W1, b1, g, beta, W2, b2 are member-indexed. With E > 0 no
+ * argument but R may be NULL. */
+int mlamg_gnn_edge_mlp_pop(const int32_t* src, const int32_t* tgt, const float* X, int F,
+                           const float* ea, int fe, int64_t E, int members, const float* W1,
+                           const float* b1, int H, const float* g, const float* beta,
+                           const float* W2, const float* b2, int64_t pstride, int C, int act,
+                           const float* R, int rc, float* out, void* stream);
+
 /* The wide layers of ns/model/ali_interp.py InterpolationNetwork (ResidualBlock of TAGConv(K=5)
  * up to 256 channels, EdgeModel 513 -> 256 -> ... -> 1 with LayerNorms), fp32, device pointers
  * (csrc/gnn_wide.hip). Conventions as above: a size outside the limit stated at a prototype

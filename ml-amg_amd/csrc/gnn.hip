@@ -27,14 +27,32 @@ constexpr int kT = 256;
   for (int64_t i = (int64_t)blockIdx.x * (per) + (sub); i < (int64_t)(n); \
        i += (int64_t)gridDim.x * (per))
 
+// A population stack (the *_pop entries): `members` equal copies of one base stack end to end,
+// member p = blockIdx.y owning rows [p M, (p + 1) M) and edges [p E, (p + 1) E), its tensor of
+// every parameter at ptr + p * pstride (0: shared weights). The three weight-consuming kernels
+// move their per-item pointers to the member's part and their weights to the member's tensors
+// once, then walk the member's items in x exactly as on a stack of their own: a block works for
+// one member, no tile straddles two, and an item's arithmetic does not see p. Node and edge ids
+// (src, tgt, tptr, teid) are ids of the whole stack, so X and msg stay where they are. The
+// single entries are members = 1 (blockIdx.y = 0: every shift is zero).
+__device__ __forceinline__ const float* member(const float* w, int64_t pstride) {
+  return w ? w + (int64_t)blockIdx.y * pstride : w;
+}
+
 // Y[m][n] = beta * Y[m][n] + sum_k X[m][k] W[n][k] (+ b[n]) -> act -> (+ R[m][n or 0]).
 // A block stages W^T in LDS (K <= 160, N <= 64) and takes 256 / NP rows at a time, NP = N
 // rounded up to a power of two; lane n of a row reads W^T[k][n] (consecutive: no conflicts) and
-// the row's X[m][k] (one address: broadcast).
+// the row's X[m][k] (one address: broadcast). M: rows per member.
 __global__ void k_linear(const float* __restrict__ X, int64_t M, int K, const float* __restrict__ W,
-                         const float* __restrict__ b, int N, int NP, int act, float beta,
-                         const float* __restrict__ R, int rc, float* __restrict__ Y) {
+                         const float* __restrict__ b, int64_t pstride, int N, int NP, int act,
+                         float beta, const float* __restrict__ R, int rc, float* __restrict__ Y) {
   extern __shared__ float wt[];  // K x N
+  const int64_t row0 = (int64_t)blockIdx.y * M;
+  W = member(W, pstride);
+  b = member(b, pstride);
+  X += row0 * K;
+  Y += row0 * N;
+  if (R) R += row0 * rc;
   for (int q = threadIdx.x; q < K * N; q += kT) {
     const int k = q / N, n = q % N;
     wt[q] = W[(int64_t)n * K + k];
@@ -126,17 +144,25 @@ __global__ void k_inorm_seg(const float* __restrict__ Xs, const int64_t* __restr
 //   h1 = relu(L1 ea + c1) (4), h2 = relu(L2 h1 + c2) (16), W_e = relu(L3 h2 + c3) [Fin x Fout],
 //   msg[e][o] = sum_i x_src[i] W_e[i][o]   (NNConv.message: x_j @ weight.view(-1, in, out))
 // A block: 64 edges (one per lane) x up to 4 output blocks of 16 (one per wave): every lane of a
-// wave reads the same L3 row (broadcast), its own source row.
+// wave reads the same L3 row (broadcast), its own source row. E: edges per member.
 __global__ void k_nnconv_msg(const int32_t* __restrict__ src, const float* __restrict__ ea,
                              int64_t E, int fe, const float* __restrict__ L1,
                              const float* __restrict__ c1, const float* __restrict__ L2,
                              const float* __restrict__ c2, const float* __restrict__ L3,
-                             const float* __restrict__ c3, const float* __restrict__ X, int Fin,
-                             int Fout, float* __restrict__ msg) {
+                             const float* __restrict__ c3, int64_t pstride,
+                             const float* __restrict__ X, int Fin, int Fout,
+                             float* __restrict__ msg) {
   const int lane = threadIdx.x & 63, ob = threadIdx.x >> 6;
   const int o0 = ob * 16;
   if (o0 >= Fout) return;
   const int no = min(16, Fout - o0);
+  const int64_t edge0 = (int64_t)blockIdx.y * E;
+  L1 = member(L1, pstride), c1 = member(c1, pstride);
+  L2 = member(L2, pstride), c2 = member(c2, pstride);
+  L3 = member(L3, pstride), c3 = member(c3, pstride);
+  src += edge0;
+  ea += edge0 * fe;
+  msg += edge0 * Fout;
   MLAMG_GRID_STRIDE(e0, E, 64, 0) {  // a tile of 64 edges; the block strides together
     const int64_t e = e0 + lane;
     const bool live = e < E;
@@ -182,13 +208,21 @@ __global__ void k_nnconv_msg(const int32_t* __restrict__ src, const float* __res
   }
 }
 
-// out[i][o] = act(sum_{incoming e} msg[e][o] + root[i][o] + bias[o]) (+ R[i][o or 0])
+// out[i][o] = act(sum_{incoming e} msg[e][o] + root[i][o] + bias[o]) (+ R[i][o or 0]); n: rows
+// per member
 __global__ void k_nnconv_aggr(const int32_t* __restrict__ tptr, const int32_t* __restrict__ teid,
                               const float* __restrict__ msg, const float* __restrict__ root,
-                              const float* __restrict__ bias, int64_t n, int F, int act,
-                              const float* __restrict__ R, int rc, float* __restrict__ Y) {
+                              const float* __restrict__ bias, int64_t pstride, int64_t n, int F,
+                              int act, const float* __restrict__ R, int rc,
+                              float* __restrict__ Y) {
   const int f = threadIdx.x & 63;
   if (f >= F) return;
+  const int64_t row0 = (int64_t)blockIdx.y * n;
+  bias = member(bias, pstride);
+  tptr += row0;
+  root += row0 * F;
+  Y += row0 * F;
+  if (R) R += row0 * rc;
   MLAMG_GRID_STRIDE(i, n, kT / 64, threadIdx.x / 64) {
     float s = 0.0f;
     for (int32_t q = tptr[i]; q < tptr[i + 1]; ++q) s += msg[(int64_t)teid[q] * F + f];
@@ -202,16 +236,25 @@ __global__ void k_nnconv_aggr(const int32_t* __restrict__ tptr, const int32_t* _
 // smallEdgeModel (agg_interp.py:37-55) and MPNN's post-ops (:124-141): a wave per edge,
 //   in = [x_src (F) | x_tgt (F) | ea (fe)], h = relu(W1 in + b1) (H <= 64, lane o),
 //   h = LayerNorm(h) * g + beta (eps 1e-5, biased variance), y_c = W2[c] . h + b2[c] (C <= 4),
-//   out = act(y) (+ R[e][c or 0]).
+//   out = act(y) (+ R[e][c or 0]). E: edges per member.
 __global__ void k_edge_mlp(const int32_t* __restrict__ src, const int32_t* __restrict__ tgt,
                            const float* __restrict__ X, int F, const float* __restrict__ ea,
                            int fe, int64_t E, const float* __restrict__ W1,
                            const float* __restrict__ b1, int H, const float* __restrict__ g,
                            const float* __restrict__ beta, const float* __restrict__ W2,
-                           const float* __restrict__ b2, int C, int act,
+                           const float* __restrict__ b2, int64_t pstride, int C, int act,
                            const float* __restrict__ R, int rc, float* __restrict__ out) {
   extern __shared__ float w1t[];  // K x H, K = 2F + fe
   const int K = 2 * F + fe;
+  const int64_t edge0 = (int64_t)blockIdx.y * E;
+  W1 = member(W1, pstride), b1 = member(b1, pstride);
+  g = member(g, pstride), beta = member(beta, pstride);
+  W2 = member(W2, pstride), b2 = member(b2, pstride);
+  src += edge0;
+  tgt += edge0;
+  ea += edge0 * fe;
+  out += edge0 * C;
+  if (R) R += edge0 * rc;
   for (int q = threadIdx.x; q < K * H; q += kT) w1t[q] = W1[(int64_t)(q % H) * K + q / H];
   __syncthreads();
   const int lane = threadIdx.x & 63;
@@ -284,6 +327,78 @@ __global__ void k_topk_seg_mark(const int32_t* __restrict__ sorted, const int64_
 inline unsigned blocks(int64_t n, int per) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 1 << 20));
 }
+// The same for n items per member with the members in y: they share the cap, so the whole grid
+// is no larger than a single launch's (16 blocks per member at 65535 members; the grid-stride
+// loop covers the rest). Sharing the cap is a choice for safety, not a tuned one: no other
+// split of the grid between x and y has been measured.
+inline dim3 blocks(int64_t n, int per, int members) {
+  return dim3((unsigned)std::max<int64_t>(
+                  1, std::min<int64_t>((n + per - 1) / per, (1 << 20) / members)),
+              (unsigned)members);
+}
+
+// What a *_pop entry refuses beyond its single entry's own limits: per = rows or edges per
+// member (two of them for the NNConv), whose stack-wide ids are int32. The Python layers call
+// the *_pop entries for every graph object, a stack of one member included, so these refusals
+// (and the *_pop entries' NULL checks, which the single NNConv and edge-model entries do not
+// make) also apply to ordinary Graph / GraphBatch inference. GraphBatch itself refuses stacks of
+// 2^31 - 1 rows or edges, so no stack it can build is turned away here; the single C entries
+// keep their own, wider limits.
+int pop_limits(int members, int64_t pstride, int64_t per_a, int64_t per_b) {
+  MLAMG_REQUIRE(members >= 1 && members <= 65535, "population: 1 <= members <= 65535");
+  MLAMG_REQUIRE(pstride >= 0, "population: pstride >= 0");
+  for (int64_t per : {per_a, per_b})
+    MLAMG_REQUIRE(per >= 0 && per < INT32_MAX && per * members < INT32_MAX,
+                  "population: members * rows and members * edges must stay below 2^31 - 1");
+  return MLAMG_OK;
+}
+
+// The three weight-consuming layers on `members` members; the single entries are members = 1.
+int linear_run(const float* X, int64_t M, int members, int K, const float* W, const float* b,
+               int64_t pstride, int N, int act, float beta, const float* R, int rc, float* Y,
+               void* stream) {
+  MLAMG_REQUIRE(M >= 0 && K >= 1 && K <= 160 && N >= 1 && N <= 64, "linear: K <= 160, N <= 64");
+  MLAMG_REQUIRE(W && (M == 0 || (X && Y)) && (!R || rc == 1 || rc == N), "linear: bad arguments");
+  if (M == 0) return MLAMG_OK;
+  int NP = 1;
+  while (NP < N) NP <<= 1;
+  const int rows = kT / NP;
+  hipLaunchKernelGGL(k_linear, blocks(M, rows, members), dim3(kT), sizeof(float) * K * N,
+                     S(stream), X, M, K, W, b, pstride, N, NP, act, beta, R, rc, Y);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int nnconv_run(const int32_t* tptr, const int32_t* teid, const int32_t* src, const float* ea,
+               int64_t E, int members, int fe, const float* L1, const float* c1, const float* L2,
+               const float* c2, const float* L3, const float* c3, int64_t pstride, const float* X,
+               int64_t n, int Fin, int Fout, const float* root, const float* bias, int act,
+               const float* R, int rc, float* msg_tmp, float* Y, void* stream) {
+  MLAMG_REQUIRE(Fout >= 1 && Fout <= 64 && Fin >= 1 && fe >= 1, "nnconv: Fout <= 64");
+  MLAMG_REQUIRE(root && bias && msg_tmp && Y, "NULL argument");
+  hipStream_t s = S(stream);
+  if (E > 0)
+    hipLaunchKernelGGL(k_nnconv_msg, blocks(E, 64, members), dim3(kT), 0, s, src, ea, E, fe, L1,
+                       c1, L2, c2, L3, c3, pstride, X, Fin, Fout, msg_tmp);
+  hipLaunchKernelGGL(k_nnconv_aggr, blocks(n, kT / 64, members), dim3(kT), 0, s, tptr, teid,
+                     msg_tmp, root, bias, pstride, n, Fout, act, R, rc, Y);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
+
+int edge_mlp_run(const int32_t* src, const int32_t* tgt, const float* X, int F, const float* ea,
+                 int fe, int64_t E, int members, const float* W1, const float* b1, int H,
+                 const float* g, const float* beta, const float* W2, const float* b2,
+                 int64_t pstride, int C, int act, const float* R, int rc, float* out,
+                 void* stream) {
+  MLAMG_REQUIRE(H >= 1 && H <= 64 && C >= 1 && C <= 4 && 2 * F + fe <= 160, "edge mlp: sizes");
+  if (E == 0) return MLAMG_OK;
+  hipLaunchKernelGGL(k_edge_mlp, blocks(E, kT / 64, members), dim3(kT),
+                     sizeof(float) * (2 * F + fe) * H, S(stream), src, tgt, X, F, ea, fe, E, W1,
+                     b1, H, g, beta, W2, b2, pstride, C, act, R, rc, out);
+  MLAMG_HIP(hipGetLastError());
+  return MLAMG_OK;
+}
 
 // top-k of every segment of a stack of n rows (seg_ptr / k_ptr null: one segment, its k = K):
 // one stable sort of (segment id | score word, node index) pairs over the bits in use, then the
@@ -327,16 +442,14 @@ extern "C" {
 
 int mlamg_gnn_linear(const float* X, int64_t M, int K, const float* W, const float* b, int N,
                      int act, float beta, const float* R, int rc, float* Y, void* stream) {
-  MLAMG_REQUIRE(M >= 0 && K >= 1 && K <= 160 && N >= 1 && N <= 64, "linear: K <= 160, N <= 64");
-  MLAMG_REQUIRE(W && (M == 0 || (X && Y)) && (!R || rc == 1 || rc == N), "linear: bad arguments");
-  if (M == 0) return MLAMG_OK;
-  int NP = 1;
-  while (NP < N) NP <<= 1;
-  const int rows = kT / NP;
-  hipLaunchKernelGGL(k_linear, dim3(blocks(M, rows)), dim3(kT), sizeof(float) * K * N, S(stream),
-                     X, M, K, W, b, N, NP, act, beta, R, rc, Y);
-  MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
+  return linear_run(X, M, 1, K, W, b, 0, N, act, beta, R, rc, Y, stream);
+}
+
+int mlamg_gnn_linear_pop(const float* X, int64_t M, int members, int K, const float* W,
+                         const float* b, int64_t pstride, int N, int act, float beta,
+                         const float* R, int rc, float* Y, void* stream) {
+  MLAMG_TRY(pop_limits(members, pstride, M, 0));
+  return linear_run(X, M, members, K, W, b, pstride, N, act, beta, R, rc, Y, stream);
 }
 
 int mlamg_gnn_gcn_norm(const int32_t* tptr, const int32_t* teid, const int32_t* src,
@@ -425,16 +538,21 @@ int mlamg_gnn_nnconv(const int32_t* tptr, const int32_t* teid, const int32_t* sr
                      const float* X, int64_t n, int Fin, int Fout, const float* root,
                      const float* bias, int act, const float* R, int rc, float* msg_tmp,
                      float* Y, void* stream) {
-  MLAMG_REQUIRE(Fout >= 1 && Fout <= 64 && Fin >= 1 && fe >= 1, "nnconv: Fout <= 64");
-  MLAMG_REQUIRE(root && bias && msg_tmp && Y, "NULL argument");
-  hipStream_t s = S(stream);
-  if (E > 0)
-    hipLaunchKernelGGL(k_nnconv_msg, dim3(blocks(E, 64)), dim3(kT), 0, s, src, ea, E, fe, L1, c1,
-                       L2, c2, L3, c3, X, Fin, Fout, msg_tmp);
-  hipLaunchKernelGGL(k_nnconv_aggr, dim3(blocks(n, kT / 64)), dim3(kT), 0, s, tptr, teid,
-                     msg_tmp, root, bias, n, Fout, act, R, rc, Y);
-  MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
+  return nnconv_run(tptr, teid, src, ea, E, 1, fe, L1, c1, L2, c2, L3, c3, 0, X, n, Fin, Fout,
+                    root, bias, act, R, rc, msg_tmp, Y, stream);
+}
+
+int mlamg_gnn_nnconv_pop(const int32_t* tptr, const int32_t* teid, const int32_t* src,
+                         const float* ea, int64_t E, int members, int fe, const float* L1,
+                         const float* c1, const float* L2, const float* c2, const float* L3,
+                         const float* c3, int64_t pstride, const float* X, int64_t n, int Fin,
+                         int Fout, const float* root, const float* bias, int act, const float* R,
+                         int rc, float* msg_tmp, float* Y, void* stream) {
+  MLAMG_TRY(pop_limits(members, pstride, n, E));
+  MLAMG_REQUIRE(tptr && X && (E == 0 || (teid && src && ea && L1 && c1 && L2 && c2 && L3 && c3)),
+                "nnconv: NULL argument");
+  return nnconv_run(tptr, teid, src, ea, E, members, fe, L1, c1, L2, c2, L3, c3, pstride, X, n,
+                    Fin, Fout, root, bias, act, R, rc, msg_tmp, Y, stream);
 }
 
 int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, int F,
@@ -442,13 +560,20 @@ int mlamg_gnn_edge_mlp(const int32_t* src, const int32_t* tgt, const float* X, i
                        int H, const float* g, const float* beta, const float* W2,
                        const float* b2, int C, int act, const float* R, int rc, float* out,
                        void* stream) {
-  MLAMG_REQUIRE(H >= 1 && H <= 64 && C >= 1 && C <= 4 && 2 * F + fe <= 160, "edge mlp: sizes");
-  if (E == 0) return MLAMG_OK;
-  hipLaunchKernelGGL(k_edge_mlp, dim3(blocks(E, kT / 64)), dim3(kT),
-                     sizeof(float) * (2 * F + fe) * H, S(stream), src, tgt, X, F, ea, fe, E, W1,
-                     b1, H, g, beta, W2, b2, C, act, R, rc, out);
-  MLAMG_HIP(hipGetLastError());
-  return MLAMG_OK;
+  return edge_mlp_run(src, tgt, X, F, ea, fe, E, 1, W1, b1, H, g, beta, W2, b2, 0, C, act, R, rc,
+                      out, stream);
+}
+
+int mlamg_gnn_edge_mlp_pop(const int32_t* src, const int32_t* tgt, const float* X, int F,
+                           const float* ea, int fe, int64_t E, int members, const float* W1,
+                           const float* b1, int H, const float* g, const float* beta,
+                           const float* W2, const float* b2, int64_t pstride, int C, int act,
+                           const float* R, int rc, float* out, void* stream) {
+  MLAMG_TRY(pop_limits(members, pstride, E, 0));
+  MLAMG_REQUIRE(E == 0 || (src && tgt && X && ea && W1 && b1 && g && beta && W2 && b2 && out),
+                "edge mlp: NULL argument");
+  return edge_mlp_run(src, tgt, X, F, ea, fe, E, members, W1, b1, H, g, beta, W2, b2, pstride, C,
+                      act, R, rc, out, stream);
 }
 
 }  // extern "C"

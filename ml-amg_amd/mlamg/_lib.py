@@ -132,6 +132,15 @@ SIGNATURES = {
     "mlamg_gnn_instance_norm_seg": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, ctypes.c_float, c_vp,
                                             c_vp]),
     "mlamg_gnn_topk_seg": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    # a population stack (FullAggNet.forward_population): members in y, weights at p * pstride
+    "mlamg_gnn_linear_pop": (c_int, [c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_i64, c_int, c_int,
+                                     ctypes.c_float, c_vp, c_int, c_vp, c_vp]),
+    "mlamg_gnn_nnconv_pop": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_int,
+                                     c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "mlamg_gnn_edge_mlp_pop": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_i64, c_int, c_vp,
+                                       c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int,
+                                       c_vp, c_int, c_vp, c_vp]),
     # the wide layers of InterpolationNetwork (csrc/gnn_wide.hip) and its host C/F splitting
     "mlamg_gnn_linear_wide": (c_int, [c_vp, c_i64, c_int, c_vp, c_vp, c_int, c_int,
                                       ctypes.c_float, c_vp, c_int, c_vp, c_vp]),

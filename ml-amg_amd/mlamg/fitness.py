@@ -1,8 +1,10 @@
 """The fitness the reference's genetic algorithm trains FullAggNet on (utils/train_dataset.py:
 81-138), in two batched steps instead of a loop over the grids: FullAggNet.forward_stack on a
 GraphBatch (every grid's aggregates and P in a fixed number of launches), then amg_2_v_batch
-(every grid's two-level solve in one launch). The GA itself (selection, mutation, the worker
-pool) stays with the caller.
+(every grid's two-level solve in one launch). evaluate_population does the same for a whole
+population of weight vectors at once (FullAggNet.forward_population on the stack of members x
+grids), with the numbers of the loop over the individuals. The GA itself (selection, mutation,
+the worker pool) stays with the caller.
 """
 from __future__ import annotations
 
@@ -89,3 +91,66 @@ def population_fitness(model, population, batch, alpha=0.3, pre_smoothing_steps=
     return np.array([1.0 / np.average(evaluate_dataset(
         model, batch, alpha, pre_smoothing_steps, post_smoothing_steps, weights=w,
         aggregation=aggregation)) for w in population])
+
+
+def evaluate_population(model, population, batch, alpha=0.3, pre_smoothing_steps=1,
+                        post_smoothing_steps=1, aggregation="pyamg", members_per_pass=None):
+    """evaluate_dataset for every row of `population` (flat weight vectors in state_dict order)
+    at once, as a (P, nb) float array: row p is exactly evaluate_dataset(model, batch, ...,
+    weights=population[p]). One FullAggNet.forward_population over the stack of P x nb graphs
+    (members_per_pass: its split into passes, which the result does not depend on), one download
+    and split of the stacked P, one amg_2_v_batch over all live (member, grid) problems; every
+    member's problem on grid g shares the host A, b and start vector of that grid. Where the
+    fused solver refuses that joint batch (some member's P has a row of P or P^T beyond its
+    slots) the solves are cut into one amg_2_v_batch per member, the loop's own batches, which
+    keeps every row exact; only the forward pass is shared then. The model's own weights are
+    neither loaded nor changed (evaluate_dataset leaves population[p] loaded)."""
+    from types import SimpleNamespace
+
+    from .multigrid import amg_2_v_batch
+    model.eval()
+    st = model.forward_population(batch, population, alpha, aggregation,
+                                  members_per_pass=members_per_pass)
+    members, nb = st["failed"].shape
+    Ps = _split_P(SimpleNamespace(seg=st["seg"], nb=members * nb),
+                  dict(st, failed=st["failed"].reshape(-1)))
+    conv = np.ones(members * nb, dtype=np.float64)
+    starts = {}
+    live, problems = [], []
+    for i, P in enumerate(Ps):
+        if P is None:
+            continue
+        g = i % nb
+        if g not in starts:
+            n = batch.As[g].shape[1]
+            x = np.random.RandomState(0).randn(n)
+            x /= np.linalg.norm(x, 2)
+            starts[g] = (np.zeros(n), x)
+        live.append(i)
+        problems.append((batch.As[g], P) + starts[g])
+    kw = dict(error_tol=1e-6, pre_smoothing_steps=pre_smoothing_steps,
+              post_smoothing_steps=post_smoothing_steps)
+    res = amg_2_v_batch(problems, fallback=False, **kw) if problems else []
+    if res is None:
+        # The fused solver plans a batch as a whole: one problem outside its slots sends every
+        # problem of the batch to the per-problem engine, whose numbers differ in the last bits.
+        # The loop's batches are one member's problems each, so cut there: a member the fused
+        # solver takes gets its launch, the others go the way they go in the loop.
+        res = []
+        for p in range(members):
+            own = [q for i, q in zip(live, problems) if i // nb == p]
+            res += amg_2_v_batch(own, **kw) if own else []
+    for i, r in zip(live, res):
+        conv[i] = r[1]
+    conv[np.isnan(conv)] = 1.0
+    return conv.reshape(members, nb)
+
+
+def population_fitness_stacked(model, population, batch, alpha=0.3, pre_smoothing_steps=1,
+                               post_smoothing_steps=1, aggregation="pyamg",
+                               members_per_pass=None):
+    """population_fitness from one evaluate_population: 1 / mean(conv factors over the batch)
+    per member, the same numbers."""
+    conv = evaluate_population(model, population, batch, alpha, pre_smoothing_steps,
+                               post_smoothing_steps, aggregation, members_per_pass)
+    return np.array([1.0 / np.average(row) for row in conv])

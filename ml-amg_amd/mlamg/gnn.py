@@ -15,6 +15,10 @@ There is one forward pass, `FullAggNet.forward_stack`, on a `GraphBatch`: many g
 block-diagonally, the per-graph steps (InstanceNorm, top-k, pyamg's sweep) done segment by
 segment. A `Graph` is a batch of one, `forward` runs it on that, `forward_batch` on many graphs at
 once, every graph's tensors bitwise its own `forward`.
+`forward_population` runs the same pass for a whole population of weight vectors at once, on a
+`PopulationBatch` (the stack repeated once per individual) with the weights taken from a
+`PopulationWeights` matrix instead of the modules: the layers' `run` methods take either source,
+and a `GraphBatch` is a population of one member.
 """
 from __future__ import annotations
 
@@ -107,6 +111,7 @@ class GraphBatch:
         np.cumsum(np.bincount(tgt, minlength=n), out=tptr[1:])
         self.As = mats
         self.nb, self.n, self.E, self.fe = len(mats), n, E, 1
+        self.members, self.member_n, self.member_E = 1, n, E  # one member: the stack itself
         self.sizes = sizes
         self.device = dev
         self.seg, self.eseg = SegPtr(seg, dev), SegPtr(eseg, dev)
@@ -206,6 +211,80 @@ class GraphBatch:
         return C, bellman_ford_pyamg_seg_device(self.plan(), C, seeds, kptr.host, fp64=fp64,
                                                 seed_ptr_dev=kptr.dev)[1]
 
+    def population(self, members):
+        """The `members`-fold PopulationBatch of this stack, cached (its Bellman-Ford plan and
+        seed offsets with it: a genetic algorithm asks for the same one every generation), with
+        this copy's node input. A replica holds `members` times the batch's device arrays, its
+        gcn weights and its plan for as long as it is cached, so the cache keeps the two sizes
+        used last — the full pass and the shorter last pass of a split population — and drops
+        the older ones. For a with_x copy of the batch the cached replica is used with that
+        input repeated, which is redone on every call."""
+        cache = self._shared.setdefault("population", {})
+        pop = cache.pop(members, None) or PopulationBatch(self, members)
+        cache[members] = pop  # most recently used last
+        while len(cache) > 2:
+            del cache[next(iter(cache))]
+        if pop._base_x is not self.x:  # a with_x copy of the batch the cached one was made from
+            pop = pop.with_x(self.x.reshape(-1).repeat(members))
+        return pop
+
+
+class PopulationBatch(GraphBatch):
+    """`members` equal copies of a GraphBatch end to end, one per individual of a population: the
+    layout of GraphBatch(batch.As * members) — member p owns rows [p n, (p + 1) n) and edges
+    [p E, (p + 1) E) of the base stack's n rows and E edges (member_n, member_E), ids are ids of
+    the whole stack, nb counts every (member, graph) segment, member-major — made from the base
+    batch's arrays where that lives, without stacking the matrices again. As is the base batch's
+    list (not repeated: every member's graph g is As[g % len(As)]). The seed offsets, the gcn
+    weights and the Bellman-Ford plan are its own, cached like a GraphBatch's. The base must be
+    a stack of canonical matrices with its original edge feature (a GraphBatch, not a
+    with_clusters copy)."""
+
+    def __init__(self, batch, members):
+        members = int(members)
+        if members < 1:
+            raise ValueError(f"a population has at least one member, got {members}")
+        if batch.fe != 1 or batch.members != 1:
+            raise ValueError("a population stack is made from a base GraphBatch")
+        for i, A in enumerate(batch.As):
+            if not A.has_canonical_format:
+                raise ValueError(f"matrix {i} of the batch has no canonical format (unsorted or "
+                                 "duplicate entries)")
+        bn, bE, dev = batch.n, batch.E, batch.device
+        n, E = members * bn, members * bE
+        if members > 65535 or n >= 2 ** 31 - 1 or E >= 2 ** 31 - 1:
+            raise ValueError("population stack exceeds 65535 members or the int32 index range")
+
+        def tiled(host, step):  # offsets without the closing entry, member after member
+            rep = host[:-1][None, :] + step * np.arange(members, dtype=np.int64)[:, None]
+            return np.concatenate([rep.ravel(), [members * step]])
+
+        def shifted(t, step, closed=False):  # a device id / offset array of the base, likewise
+            base = t[:-1] if closed else t
+            off = torch.arange(members, dtype=torch.int64, device=dev) * step
+            out = (base.long()[None, :] + off[:, None]).reshape(-1)
+            if closed:
+                out = torch.cat([out, out.new_tensor([members * step])])
+            return out.to(torch.int32)
+
+        self.As = batch.As
+        self.nb, self.n, self.E, self.fe = members * batch.nb, n, E, 1
+        self.members, self.member_n, self.member_E = members, bn, bE
+        self.sizes = np.tile(batch.sizes, members)
+        self.device = dev
+        self.seg = SegPtr(tiled(batch.seg.host, bn), dev)
+        self.eseg = SegPtr(tiled(batch.eseg.host, bE), dev)
+        self.crow = shifted(batch.crow, bE, closed=True)
+        self.src = shifted(batch.src, bn)
+        self.tgt = shifted(batch.tgt, bn)
+        self.tptr = shifted(batch.tptr, bE, closed=True)
+        self.teid = shifted(batch.teid, bE)
+        self.edge_attr = batch.edge_attr.repeat(members, 1)
+        self.x = batch.x.repeat(members, 1)
+        self._base_x = batch.x
+        self.edge_index = torch.stack([self.src.long(), self.tgt.long()])
+        self._shared = {"kptr": {}}
+
 
 class Graph(GraphBatch):
     """One graph: graph_from_matrix_basic(A) / graph_from_matrix(A, agg) (ns/model/data.py:22-46)
@@ -234,15 +313,84 @@ class Graph(GraphBatch):
         return C, bellman_ford_pyamg_device(C, seeds, fp64=fp64)[1]
 
 
+# ----------------------------------------------------------------------------------- weights
+class ModuleWeights:
+    """Where a layer's run() takes its weights from: here the module's own parameters, one set
+    shared by every member of the stack (pstride 0). Called with a parameter (or None), returns
+    the tensor the kernel reads for member 0; member p's lies pstride floats further on."""
+    pstride = 0
+
+    def __call__(self, p):
+        return None if p is None else p.detach().contiguous()
+
+
+OWN = ModuleWeights()
+
+
+class PopulationWeights(ModuleWeights):
+    """The weights of a whole population for `model`'s layers: `population` is a (P, total)
+    array of flat vectors in state_dict order (fitness.weights_as_vector's layout), uploaded once
+    as one fp32 (P, total) tensor on the model's device (`data`; rounded like weights_as_dict's
+    .to(float32)). Called with one of the model's parameters it returns member 0's tensor of it,
+    a view into row 0; member p's lies pstride = total floats further on, which is how the *_pop
+    kernels index it. view(name, member) is any member's tensor by state_dict name. The model's
+    own parameters are neither read nor written."""
+
+    def __init__(self, model, population):
+        sd = model.state_dict()
+        pop = np.asarray(population)
+        total = sum(v.numel() for v in sd.values())
+        if pop.ndim != 2 or pop.shape[0] < 1:
+            raise ValueError("a population is a (P, total) array with P >= 1, got shape "
+                             f"{pop.shape}")
+        if pop.shape[1] != total:
+            raise ValueError(f"weight vectors have {pop.shape[1]} entries, the model {total}")
+        if any(v.dtype != torch.float32 for v in sd.values()):
+            raise ValueError("a population stack takes a model whose tensors are all float32")
+        dev = next(model.parameters()).device
+        self.data = torch.as_tensor(np.ascontiguousarray(pop)).to(torch.float32).to(dev)
+        self.members, self.pstride = int(pop.shape[0]), int(total)
+        tensors = dict(model.named_parameters())
+        tensors.update(model.named_buffers())
+        self.layout, self._at, at = {}, {}, 0
+        for name, v in sd.items():
+            self.layout[name] = (at, tuple(v.shape))
+            self._at[id(tensors[name])] = name
+            at += v.numel()
+        self._tensors = tensors  # kept alive: the ids above are theirs
+
+    def view(self, name, member=0):
+        at, shape = self.layout[name]
+        return self.data[member, at:at + int(np.prod(shape, dtype=np.int64))].view(shape)
+
+    def __call__(self, p):
+        if p is None:
+            return None
+        if id(p) not in self._at:
+            raise KeyError("not a parameter of the model this population was made for")
+        return self.view(self._at[id(p)])
+
+    def rows(self, a, b):
+        """Members a .. b - 1 as a population of their own (views, nothing copied)."""
+        w = object.__new__(type(self))
+        w.__dict__.update(self.__dict__)
+        w.data, w.members = self.data[a:b], b - a
+        return w
+
+
 # ------------------------------------------------------------------------------------ kernels
-def linear(x, W, b=None, act=0, out=None, beta=0.0, residual=None):
+def linear(x, W, b=None, act=0, out=None, beta=0.0, residual=None, members=1, w=OWN):
+    """members, w: the rows of x are `members` equal parts, part p on member p's W and b of the
+    weight source w (OWN: W and b themselves, shared)."""
     x = x.contiguous()
     M, K = x.shape
     N = W.shape[0]
+    if M % members:
+        raise ValueError(f"{M} rows are not {members} equal parts")
     y = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=x.device)
     rc = 0 if residual is None else residual.shape[1]
-    call("mlamg_gnn_linear", ptr(x), int(M), int(K), ptr(W.detach().contiguous()),
-         _p(None if b is None else b.detach().contiguous()), int(N), int(act), float(beta),
+    call("mlamg_gnn_linear_pop", ptr(x), int(M // members), int(members), int(K), ptr(w(W)),
+         _p(w(b)), int(w.pstride), int(N), int(act), float(beta),
          _p(None if residual is None else residual.contiguous()), int(rc), ptr(y), stream_ptr())
     return y
 
@@ -296,6 +444,42 @@ def topk_vec_seg(x, seg, kptr):
     return vec, idx[:int(kptr.host[-1])]
 
 
+POPULATION_SCRATCH_BYTES = 2 << 30  # FullAggNet.members_per_pass: NNConv messages of one pass
+
+
+def _join_passes(passes, stacks):
+    """forward_stack's dicts of consecutive passes of a population as the dict of the whole
+    stack: rows, aggregate columns and seed offsets of a pass shifted behind the earlier ones,
+    every entry's own bits kept."""
+    from .sparse import DeviceCSR
+    rows = np.concatenate([[0], np.cumsum([s.n for s in stacks])])
+    cols = np.concatenate([[0], np.cumsum([int(st["kptr"].host[-1]) for st in passes])])
+    dev = stacks[0].device
+
+    def offsets(ptrs, shifts):
+        return np.concatenate([p.host[:-1] + s for p, s in zip(ptrs, shifts)]
+                              + [[ptrs[-1].host[-1] + shifts[len(ptrs) - 1]]])
+
+    def csr(key, coff):
+        crows, cjs, vals, nnz = [], [], [], 0
+        for i, st in enumerate(passes):
+            crow, cj, v = st[key].to_torch()
+            crows.append((crow if i == 0 else crow[1:]).long() + nnz)
+            cjs.append(cj.long() + int(coff[i]))
+            vals.append(v)
+            nnz += int(st[key].nnz)
+        return DeviceCSR.from_torch(torch.cat(crows).to(torch.int32),
+                                    torch.cat(cjs).to(torch.int32), torch.cat(vals),
+                                    (int(rows[-1]), int(coff[-1])))
+
+    return dict(Agg=csr("Agg", cols), P=csr("P", cols), C=csr("C", rows),
+                top_k=torch.cat([st["top_k"] + int(r) for st, r in zip(passes, rows)]),
+                node_scores=torch.cat([st["node_scores"] for st in passes]),
+                kptr=SegPtr(offsets([st["kptr"] for st in passes], cols), dev),
+                seg=SegPtr(offsets([s.seg for s in stacks], rows), dev),
+                failed=np.concatenate([np.asarray(st["failed"]).reshape(-1) for st in passes]))
+
+
 # ------------------------------------------------------------------------------------ modules
 class TensorLambda(nn.Module):
     """Parameter-free placeholder at index 0 of NNConv's edge network (agg_interp.py:24-34)."""
@@ -318,14 +502,16 @@ class TAGConv(nn.Module):
                                    for _ in range(K + 1)])
         self.bias = nn.Parameter(torch.zeros(out_channels))
 
-    def run(self, g, x, act=0):
+    def run(self, g, x, act=0, w=OWN):
+        """w (here and in every layer below): the weight source, the module's own parameters or
+        a PopulationWeights with one member per member of g."""
         wn = g.gcn_weights()
-        out = linear(x, self.lins[0].weight)
+        out = linear(x, self.lins[0].weight, members=g.members, w=w)
         for k in range(1, self.K + 1):
             x = propagate(g, wn, x)
             last = k == self.K
             out = linear(x, self.lins[k].weight, b=self.bias if last else None,
-                         act=act if last else 0, out=out, beta=1.0)
+                         act=act if last else 0, out=out, beta=1.0, members=g.members, w=w)
         return out
 
 
@@ -342,22 +528,22 @@ class NNConv(nn.Module):
         self.lin = nn.Linear(in_channels, out_channels, bias=False)
         self.bias = nn.Parameter(torch.zeros(out_channels))
 
-    def run(self, g, x, ea, act=0, residual=None):
+    def run(self, g, x, ea, act=0, residual=None, w=OWN):
         x = x.contiguous()
         ea = ea.contiguous()
         n = x.shape[0]
-        root = linear(x, self.lin.weight)
+        root = linear(x, self.lin.weight, members=g.members, w=w)
         msg = torch.empty((max(g.E, 1), self.out_channels), dtype=torch.float32, device=x.device)
         y = torch.empty((n, self.out_channels), dtype=torch.float32, device=x.device)
         L1, L2, L3 = self.nn[1], self.nn[3], self.nn[5]
         rc = 0 if residual is None else residual.shape[1]
-        call("mlamg_gnn_nnconv", ptr(g.tptr), ptr(g.teid), ptr(g.src), ptr(ea), int(g.E),
-             int(ea.shape[1]), ptr(L1.weight.detach()), ptr(L1.bias.detach()),
-             ptr(L2.weight.detach()), ptr(L2.bias.detach()), ptr(L3.weight.detach()),
-             ptr(L3.bias.detach()), ptr(x), int(n), int(self.in_channels),
-             int(self.out_channels), ptr(root), ptr(self.bias.detach()), int(act),
-             _p(None if residual is None else residual.contiguous()), int(rc), ptr(msg), ptr(y),
-             stream_ptr())
+        call("mlamg_gnn_nnconv_pop", ptr(g.tptr), ptr(g.teid), ptr(g.src), ptr(ea),
+             int(g.member_E), int(g.members), int(ea.shape[1]), ptr(w(L1.weight)),
+             ptr(w(L1.bias)), ptr(w(L2.weight)), ptr(w(L2.bias)), ptr(w(L3.weight)),
+             ptr(w(L3.bias)), int(w.pstride), ptr(x), int(n // g.members),
+             int(self.in_channels), int(self.out_channels), ptr(root), ptr(w(self.bias)),
+             int(act), _p(None if residual is None else residual.contiguous()), int(rc),
+             ptr(msg), ptr(y), stream_ptr())
         return y
 
 
@@ -369,17 +555,17 @@ class SmallEdgeModel(nn.Module):
         self.edge_mlp = nn.Sequential(nn.Linear(in_dim, hid_dim), nn.ReLU(),
                                       nn.LayerNorm([hid_dim]), nn.Linear(hid_dim, out_dim))
 
-    def run(self, g, x, ea, act=0, residual=None):
+    def run(self, g, x, ea, act=0, residual=None, w=OWN):
         l1, ln, l2 = self.edge_mlp[0], self.edge_mlp[2], self.edge_mlp[3]
         x = x.contiguous()
         ea = ea.contiguous()
         C = l2.weight.shape[0]
         out = torch.empty((max(g.E, 1), C), dtype=torch.float32, device=x.device)
         rc = 0 if residual is None else residual.shape[1]
-        call("mlamg_gnn_edge_mlp", ptr(g.src), ptr(g.tgt), ptr(x), int(x.shape[1]), ptr(ea),
-             int(ea.shape[1]), int(g.E), ptr(l1.weight.detach()), ptr(l1.bias.detach()),
-             int(l1.weight.shape[0]), ptr(ln.weight.detach()), ptr(ln.bias.detach()),
-             ptr(l2.weight.detach()), ptr(l2.bias.detach()), int(C), int(act),
+        call("mlamg_gnn_edge_mlp_pop", ptr(g.src), ptr(g.tgt), ptr(x), int(x.shape[1]), ptr(ea),
+             int(ea.shape[1]), int(g.member_E), int(g.members), ptr(w(l1.weight)),
+             ptr(w(l1.bias)), int(l1.weight.shape[0]), ptr(w(ln.weight)), ptr(w(ln.bias)),
+             ptr(w(l2.weight)), ptr(w(l2.bias)), int(w.pstride), int(C), int(act),
              _p(None if residual is None else residual.contiguous()), int(rc), ptr(out),
              stream_ptr())
         return out[:g.E]
@@ -403,16 +589,17 @@ class MPNN(nn.Module):
         self.edge_conv_out = SmallEdgeModel(4, dim, 1)
 
     @torch.no_grad()
-    def run(self, g):
+    def run(self, g, w=OWN):
         x = g.x
         ea = g.edge_attr
-        x = self.node_conv_in.run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x)
-        ea = self.edge_conv_in.run(g, x, ea, act=1, residual=ea)
+        x = self.node_conv_in.run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x, w=w)
+        ea = self.edge_conv_in.run(g, x, ea, act=1, residual=ea, w=w)
         for i in range(self.num_internal_conv):
-            x = self.node_convs[i].run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x)
-            ea = self.edge_convs[i].run(g, x, ea, act=1, residual=ea)
-        x = self.node_conv_out.run(g, instance_norm_seg(x, g.seg), ea, act=1)
-        ea = self.edge_conv_out.run(g, x, ea, act=1)
+            x = self.node_convs[i].run(g, instance_norm_seg(x, g.seg), ea, act=1, residual=x,
+                                       w=w)
+            ea = self.edge_convs[i].run(g, x, ea, act=1, residual=ea, w=w)
+        x = self.node_conv_out.run(g, instance_norm_seg(x, g.seg), ea, act=1, w=w)
+        ea = self.edge_conv_out.run(g, x, ea, act=1, w=w)
         return x, ea
 
 
@@ -438,21 +625,21 @@ class AggBinarizationLayer(nn.Module):
         self.num_conv = num_conv
         self.dim = dim
 
-    def run_raw(self, g, x):
+    def run_raw(self, g, x, w=OWN):
         if x.dim() == 1:
             x = x.unsqueeze(1)
         for i in range(self.num_conv):
             x = instance_norm_seg(x, g.seg)
-            x = self.ncs[i].run(g, x, act=1)        # relu(TAGConv(x))
+            x = self.ncs[i].run(g, x, act=1, w=w)   # relu(TAGConv(x))
             for lin in self.fcs[i]:
                 if isinstance(lin, nn.Linear):
-                    x = linear(x, lin.weight, lin.bias, act=1)
+                    x = linear(x, lin.weight, lin.bias, act=1, members=g.members, w=w)
         return x
 
     @torch.no_grad()
-    def run(self, g, x, k):
+    def run(self, g, x, k, w=OWN):
         """k: the seed offsets per graph (SegPtr); one graph alone also takes its seed count."""
-        return topk_vec_seg(self.run_raw(g, x), g.seg, g.seed_ptr(k))[0]
+        return topk_vec_seg(self.run_raw(g, x, w), g.seg, g.seed_ptr(k))[0]
 
 
 class AggNet(nn.Module):
@@ -465,10 +652,10 @@ class AggNet(nn.Module):
         self.num_iterations = iterations
 
     @torch.no_grad()
-    def run(self, g, k):
+    def run(self, g, k, w=OWN):
         x = g.x
         for layer in self.layers:
-            x = layer.run(g, x, k)
+            x = layer.run(g, x, k, w)
         return x
 
 
@@ -516,7 +703,8 @@ class FullAggNet(nn.Module):
         return (to_t(st["Agg"]), to_t(st["P"]), to_t(st["C"]), st["top_k"], st["node_scores"])
 
     @torch.no_grad()
-    def forward_stack(self, batch, alpha, aggregation="pyamg", x=None, strict=False):
+    def forward_stack(self, batch, alpha, aggregation="pyamg", x=None, strict=False,
+                      weights=None):
         """The forward pass (:442-486) on every graph of `batch`, a GraphBatch or a Graph (a
         batch of one; nothing else is accepted), at once, results still stacked: a dict with
         Agg, P, C (DeviceCSR on stack rows; Agg and P on stacked aggregate columns; C as pyamg
@@ -525,17 +713,23 @@ class FullAggNet(nn.Module):
         (numpy bool per graph: some node reached by no seed; "parallel" never fails; strict:
         KeyError(-1) instead, before PNet runs). Every step is one call on the stack, so
         launches and host synchronisations do not depend on the batch size, and every graph's
-        part carries the bits it has when the graph runs alone."""
+        part carries the bits it has when the graph runs alone. weights: a PopulationWeights
+        with one member per member of a PopulationBatch, instead of the model's own parameters
+        (forward_population)."""
         from .graph import aggregate_op_device, bellman_ford_device, labels_to_columns
         if aggregation not in ("pyamg", "pyamg64", "parallel"):
             raise ValueError("aggregation must be 'pyamg', 'pyamg64' or 'parallel', got "
                              f"{aggregation!r}")
+        w = OWN if weights is None else weights
+        if weights is not None and weights.members != batch.members:
+            raise ValueError(f"{weights.members} weight sets for a stack of {batch.members} "
+                             "members")
         g = batch if x is None else batch.with_x(x)
         kptr = batch.k_ptr(alpha)
-        node_scores = self.AggNet.run(g, kptr).reshape(-1)
+        node_scores = self.AggNet.run(g, kptr, w).reshape(-1)
         top_k = torch.nonzero(node_scores == 1).reshape(-1)  # k_g per graph, graph after graph
         # Bellman-Ford over the CNet edge weights from the seeds (:466-475), on the device
-        _, bf_edges = self.CNet.run(g)
+        _, bf_edges = self.CNet.run(g, w)
         C = g.csr(bf_edges)
         seeds = top_k.to(torch.int32)
         failed = np.zeros(batch.nb, dtype=bool)
@@ -554,10 +748,64 @@ class FullAggNet(nn.Module):
         col = labels_to_columns(lab, seeds)
         Agg = aggregate_op_device(col, int(kptr.host[-1]))
         # P_hat from PNet on graph_from_matrix(A, Agg), P = P_hat Agg (:476-484)
-        _, p_edges = self.PNet.run(g.with_clusters(col))
+        _, p_edges = self.PNet.run(g.with_clusters(col), w)
         P = g.csr(p_edges) @ Agg
         return dict(Agg=Agg, P=P, C=C, top_k=top_k, node_scores=node_scores, kptr=kptr,
                     failed=failed)
+
+    def members_per_pass(self, batch):
+        """The default split of forward_population: the largest number of members whose stack
+        of `batch` stays inside the kernels' limits (65535 members, fewer than 2^31 - 1 rows
+        and edges) and whose NNConv messages, members * E * dim * 4 bytes — the dominant
+        scratch term of a pass — stay inside POPULATION_SCRATCH_BYTES (2 GiB)."""
+        dim = self.AggNet.layers[0].dim
+        by_index = (2 ** 31 - 2) // max(batch.n, batch.E, 1)
+        by_scratch = POPULATION_SCRATCH_BYTES // max(batch.E * dim * 4, 1)
+        return int(max(1, min(65535, by_index, by_scratch)))
+
+    @torch.no_grad()
+    def forward_population(self, batch, population, alpha, aggregation="pyamg", x=None,
+                           members_per_pass=None):
+        """forward_stack for every individual of a population at once: `population` is a
+        (P, total) array of flat weight vectors in state_dict order (or a PopulationWeights made
+        from one), `batch` the GraphBatch of nb graphs they are all scored on. Returns
+        forward_stack's dict for the stack of P x nb graphs, member-major (member p's graph g
+        is segment p nb + g: rows, aggregate columns, top_k and kptr all run over that stack),
+        with `failed` of shape (P, nb) and `seg`, the stack's node offsets (SegPtr). Member p's
+        part is bitwise forward_stack(batch, ...) after load_state_dict(weights_as_dict(model,
+        population[p])); the model's own parameters are neither read nor written.
+
+        The stack is batch.population(m) (a PopulationBatch, cached on the batch with its
+        Bellman-Ford plan); the three weight-consuming kernels take member p's tensors from row p
+        of the population (mlamg_gnn_*_pop), every other step sees P x nb segments.
+        members_per_pass splits the population into consecutive passes of that many members (the
+        last may be shorter), whose results are joined; the default is self.members_per_pass(
+        batch). The results do not depend on the split; the joined stack itself must fit int32
+        row and entry counts. Whether one pass is faster than P forward_stack calls is
+        unmeasured (tools/bench_gnn_population.py is the benchmark). x: the
+        per-node input hook of forward(), for the nb graphs (every member gets the same)."""
+        pw = population if isinstance(population, PopulationWeights) \
+            else PopulationWeights(self, population)
+        P = pw.members
+        chunk = int(members_per_pass) if members_per_pass else self.members_per_pass(batch)
+        if chunk < 1:
+            raise ValueError("members_per_pass must be at least 1")
+        if x is not None:
+            x = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x,
+                                dtype=torch.float32).reshape(-1)
+        passes, stacks = [], []
+        for a in range(0, P, chunk):
+            m = min(chunk, P - a)
+            pb = batch.population(m)
+            stacks.append(pb)
+            passes.append(self.forward_stack(pb, alpha, aggregation,
+                                             None if x is None else x.repeat(m),
+                                             weights=pw.rows(a, a + m)))
+        st = passes[0] if len(passes) == 1 else _join_passes(passes, stacks)
+        if len(passes) == 1:
+            st["seg"] = stacks[0].seg
+        st["failed"] = st["failed"].reshape(P, batch.nb)
+        return st
 
     @torch.no_grad()
     def forward_batch(self, batch, alpha, aggregation="pyamg", x=None, strict=False):

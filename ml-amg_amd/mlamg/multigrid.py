@@ -605,11 +605,16 @@ def amg_2_v_batch(problems, workers=8, **kw):
 
     Problems within the fused solver's limits (all of the reference's small-grid datasets) run
     together in ONE launch, one workgroup each (csrc/batch.hip); the rest go through the
-    threaded per-problem path below."""
+    threaded per-problem path below. The launch is planned for the batch as a whole: one
+    problem outside the fused kernel's slots (a row of P or P^T too long) sends every problem
+    of its batch to the per-problem path, whose numbers differ from the fused solver's in the
+    last bits. fallback=False returns None in that case, before anything is launched, so that a
+    caller can choose how to cut the batch (fitness.evaluate_population)."""
     import threading
     from concurrent.futures import ThreadPoolExecutor
     problems = list(problems)
     engine = kw.pop("engine", "auto")
+    fallback = kw.pop("fallback", True)
     if engine != "hierarchy" and problems:
         opts = dict(pre_smoothing_steps=1, post_smoothing_steps=1, jacobi_weight=0.666,
                     res_tol=None, error_tol=None, max_iter=500, singular=False,
@@ -635,6 +640,8 @@ def amg_2_v_batch(problems, workers=8, **kw):
                                  opts["post_smoothing_steps"], opts["jacobi_weight"],
                                  opts["res_tol"], opts["error_tol"], opts["max_iter"],
                                  opts["smoother"])
+            if out is None and not fallback:
+                return None
             if out is not None:
                 for i, o in zip(idx, out):
                     results[i] = o
